@@ -9,6 +9,8 @@ per-rank lnL (site sharding).  Inputs are resident in HBM before
 the timed region (tips uploaded once, as TreeModel.initialise does).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4]
+    python bench.py ... --full              # + every leg beside the headline figure (below)
+    python bench.py ... --dump-outputs DIR  # + the last timed step's outputs, DIR/<name>.npy
     python bench.py --workload edges [--config ...]   # SURVEY 8(f) N1, secondary line
     python bench.py --config cfg5                      # tree sharding
 
@@ -17,6 +19,12 @@ the same tree, so per-GPU work is fixed as N grows.  `--total-sites T` is the st
 (BASELINE cfg4 as stated: ONE T-site alignment split over the N ranks; the alignment is
 simulated in fixed 125k-site blocks, block b from seed 1000 + b, so every N sees the same
 sites and `config.total_sites` stays T).
+
+A run without --full does what the headline figure needs and no more: set-up, the W warm-up
+steps (and --warm-seconds of further untimed steps, for the clocks), exactly K timed steps, the
+result line.  --full adds, after the timed steps, the legs that take runs of their own: the
+per-launch event pass and roofline, the write-ceiling probe, the CPU baselines with the accuracy
+figures, the multi-rank oracle check.
 """
 import argparse
 import glob
@@ -110,6 +118,38 @@ def warm_for(seconds, batch, world, dev=None):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 64_000_000  # bytes of --dump-outputs files in all
+
+
+def dump_sample(a, cap):
+    """`a` as a float64 array of at most `cap` bytes: the whole array, or -- a larger one --
+    the rows (first axis) of a fixed, seeded sample of its row indices, in ascending order."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    row = max(1, a.nbytes // max(1, a.shape[0]))
+    keep = int(cap // row)
+    if a.shape[0] <= keep:
+        return a
+    if keep < 1:
+        raise ValueError("one row of a %s array exceeds the %d-byte share" % (a.shape, cap))
+    idx = np.sort(np.random.default_rng(20240229).choice(a.shape[0], size=keep, replace=False))
+    return np.ascontiguousarray(a[idx])
+
+
+def dump_outputs(directory, rank, world, arrays):
+    """--dump-outputs: `arrays` {name: array} as <directory>/<name>.npy (float64), every file
+    at most an equal share of DUMP_BUDGET (dump_sample).  Every rank of a multi-rank run
+    writes its own <name>.rank<r>.npy."""
+    os.makedirs(directory, exist_ok=True)
+    cap = (DUMP_BUDGET - 1024 * len(arrays)) // len(arrays)  # .npy headers: < 1 KB each
+    for name, a in arrays.items():
+        fname = name if world == 1 else "%s.rank%d" % (name, rank)
+        np.save(os.path.join(directory, fname + ".npy"), dump_sample(a, cap))
+    log("[bench] rank %d: outputs of the last timed step written to %s (%s)"
+        % (rank, directory, ", ".join(arrays)))
 
 
 def spawn_ranks(n, argv=None):
@@ -434,14 +474,27 @@ def main():
                          "`sites` per rank")
     ap.add_argument("--trees", type=int, default=0,
                     help="cfg5: trees per rank (override; default the config's 125)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the "
+                         "headline figure: the per-launch event times and roofline, the "
+                         "write-ceiling probe, the CPU baselines and accuracy figures, the "
+                         "multi-rank oracle check (the --no-* options below leave parts of it "
+                         "out).  Without it a run sets up, warms up, times the steps and prints "
+                         "the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last timed step computed as "
+                         "DIR/<name>.npy (float64; at most 64 MB in all, larger arrays as a "
+                         "fixed seeded sample of their rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--no-ceiling", action="store_true",
-                    help="skip the same-device write-ceiling probe of the roofline")
+                    help="--full without the same-device write-ceiling probe of the roofline")
     ap.add_argument("--no-rank-check", action="store_true",
-                    help="skip the multi-rank oracle check of the job's lnL (world > 1)")
+                    help="--full without the multi-rank oracle check of the job's lnL "
+                         "(world > 1)")
     ap.add_argument("--events", choices=["timed", "separate"], default="separate",
-                    help="where the per-launch HIP events for the roofline are recorded: in "
-                         "the timed steps (timed) or in a second pass of the same steps right "
+                    help="--full: where the per-launch HIP events for the roofline are recorded: "
+                         "in the timed steps (timed) or in a second pass of the same steps right "
                          "after them, so that the event packets do not sit in the timed "
                          "region (separate, default: they cost 7-10 us per step inside it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -466,6 +519,13 @@ def main():
         cfg["desc"] += " [--trees %d override]" % args.trees
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if not args.full:
+        if args.events == "timed":
+            sys.exit("bench.py: --events timed records the roofline's events: it needs --full")
+        # the headline figure alone: none of the runs beside the timed steps
+        args.no_cpu_baseline = args.no_ceiling = args.no_rank_check = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start the N ranks ourselves (nothing has touched the GPU)
         sys.exit(spawn_ranks(args.gpus))
@@ -656,44 +716,22 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     lnl_total = float(ring.last().item())  # the last step's lnL
-    if args.events == "separate":
-        mode["graph"] = False  # the events are recorded by pu_enqueue itself
-        N.check(N.lib().pu_ctx_profile(ctx, 1), ctx)
-        for _ in range(args.steps):
-            step()
-        drain()
-
-    ev = event_times(ctx, args.steps)
-    N.check(N.lib().pu_ctx_profile(ctx, 0), ctx)
-    torch.cuda.synchronize(dev)
+    if args.dump_outputs:
+        # what the last timed step left for a caller: the job's lnL (TreeModel.likelihood), this
+        # rank's per-pattern lnL (sitewise_patterns) and root partials and scalers
+        # (compute_partials_at_edge on the root edge)
+        site_out, root_p, root_s = np.zeros(S), np.zeros((S, C, K)), np.zeros((S, C))
+        N.check(N.lib().pu_get_site_lnl(ctx, N.ptr(site_out)), ctx, "pu_get_site_lnl")
+        N.check(N.lib().pu_get_root(ctx, N.ptr(root_p), N.ptr(root_s)), ctx, "pu_get_root")
+        dump_outputs(args.dump_outputs, rank, world,
+                     {"lnl": np.array([lnl_total]), "site_lnl": site_out,
+                      "root_partials": root_p, "root_scale": root_s})
 
     updates_per_step = (ntax - 1) * S * C       # (N-2) ops + root combine, per rank
     # the job's updates per step: every rank's (weak: equal shards; strong: T sites in all)
     job_updates = (ntax - 1) * args.total_sites * C if strong else updates_per_step * world
     total_updates = job_updates * args.steps
     value = total_updates / elapsed / 1e6
-    # SURVEY 8(d) M3: 8*(3K+3) B per update (2 child CLVs + parent + 3 scalers, tips as
-    # dense fp64) + root scalers read + sitewise output
-    alg_bytes = updates_per_step * 8 * (3 * K + 3) + S * C * 8 + S * 8
-    tag = pmc_tag(args.config, S, args.lnl_only, override=bool(args.sites))
-    roofline = traversal_roofline(ctx, ev, tag, alg_bytes, updates_per_step, K, args.lnl_only)
-    roofline["events_pass"] = ("a second pass of the same %d steps right after the timed one"
-                               % args.steps if args.events == "separate"
-                               else "the timed steps")
-    if roofline.get("unit") == "GB/s" and not args.no_ceiling:
-        # the same device's write-stream ceiling for the bytes one launch moves, after the
-        # timed steps (r06): how far this box's HBM lets any store stream go, so that a slow
-        # box shows as a low ceiling and a slow kernel as a low frac_of_ceiling
-        nbytes = int(roofline["traffic"] or roofline["compulsory_bytes_per_launch"])
-        cms = ctypes.c_double()
-        N.check(N.lib().pu_write_ceiling(dev.index, nbytes, 50, ctypes.byref(cms)), None,
-                "pu_write_ceiling")
-        ceil_gbs = nbytes / (cms.value * 1e-3) / 1e9
-        roofline["ceiling_GBps"] = round(ceil_gbs, 1)
-        roofline["frac_of_ceiling"] = round(roofline["achieved"] / ceil_gbs, 4)
-        roofline["ceiling_probe"] = ("hipMemsetAsync of the launch's %d bytes, median of 50 after "
-                                     "3 warm-ups (pu_write_ceiling): the fastest write stream "
-                                     "measured on MI355X (DESIGN 4.1)" % nbytes)
     out = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -720,14 +758,54 @@ def main():
                              if graphs is not None else "eager launches",
                    "parallelism": "site-sharded x%d, RCCL lnL all-reduce overlapped with the "
                                   "next step's kernels" % world},
-        "roofline": roofline,
-        "timing": {"source": "hipEvents on the launch stream around each timed step",
-                   "runs": ev["n"], "step_ms_median": ev["step_med"],
-                   "kernel_ms_median": ev["trav_med"], "kernel_ms_mean": ev["trav_mean"],
-                   "value_at_step_median": round(job_updates / (ev["step_med"] * 1e-3) / 1e6,
-                                                 3)},
         "lnl": lnl_total,
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    if args.events == "separate":
+        mode["graph"] = False  # the events are recorded by pu_enqueue itself
+        N.check(N.lib().pu_ctx_profile(ctx, 1), ctx)
+        for _ in range(args.steps):
+            step()
+        drain()
+
+    ev = event_times(ctx, args.steps)
+    N.check(N.lib().pu_ctx_profile(ctx, 0), ctx)
+    torch.cuda.synchronize(dev)
+
+    # SURVEY 8(d) M3: 8*(3K+3) B per update (2 child CLVs + parent + 3 scalers, tips as
+    # dense fp64) + root scalers read + sitewise output
+    alg_bytes = updates_per_step * 8 * (3 * K + 3) + S * C * 8 + S * 8
+    tag = pmc_tag(args.config, S, args.lnl_only, override=bool(args.sites))
+    roofline = traversal_roofline(ctx, ev, tag, alg_bytes, updates_per_step, K, args.lnl_only)
+    roofline["events_pass"] = ("a second pass of the same %d steps right after the timed one"
+                               % args.steps if args.events == "separate"
+                               else "the timed steps")
+    if roofline.get("unit") == "GB/s" and not args.no_ceiling:
+        # the same device's write-stream ceiling for the bytes one launch moves, after the
+        # timed steps (r06): how far this box's HBM lets any store stream go, so that a slow
+        # box shows as a low ceiling and a slow kernel as a low frac_of_ceiling
+        nbytes = int(roofline["traffic"] or roofline["compulsory_bytes_per_launch"])
+        cms = ctypes.c_double()
+        N.check(N.lib().pu_write_ceiling(dev.index, nbytes, 50, ctypes.byref(cms)), None,
+                "pu_write_ceiling")
+        ceil_gbs = nbytes / (cms.value * 1e-3) / 1e9
+        roofline["ceiling_GBps"] = round(ceil_gbs, 1)
+        roofline["frac_of_ceiling"] = round(roofline["achieved"] / ceil_gbs, 4)
+        roofline["ceiling_probe"] = ("hipMemsetAsync of the launch's %d bytes, median of 50 after "
+                                     "3 warm-ups (pu_write_ceiling): the fastest write stream "
+                                     "measured on MI355X (DESIGN 4.1)" % nbytes)
+    out["roofline"] = roofline
+    out["timing"] = {"source": "hipEvents on the launch stream around each timed step",
+                     "runs": ev["n"], "step_ms_median": ev["step_med"],
+                     "kernel_ms_median": ev["trav_med"], "kernel_ms_mean": ev["trav_mean"],
+                     "value_at_step_median": round(job_updates / (ev["step_med"] * 1e-3) / 1e6,
+                                                   3)}
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         site_gpu = np.zeros(S)
@@ -972,6 +1050,8 @@ def bench_trees(args, cfg, world, rank, local_rank, dev):
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     got = lnl.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"lnl_trees": got})
     max_rel = float(np.max(np.abs(got - ref) / np.abs(ref)))
     # the oracle on this rank's trees (as many as fit --cpu-seconds; every tree at cfg5's
     # size): rank 0 of a one-GPU run reports it as cpu_baseline, every rank of a multi-rank
@@ -998,7 +1078,9 @@ def bench_trees(args, cfg, world, rank, local_rank, dev):
     value = upd_tree * T * world * args.steps / elapsed / 1e6
     alg = upd_tree * 8 * (3 * K + 3) + S * C * 8 + S * 8
     n_ev = max(20, min(args.steps, 200))
-    if tbatch is not None:
+    if not args.full:
+        roofline = None  # the event passes below are runs of their own
+    elif tbatch is not None:
         # the batched traversal launch (all T trees), events around it on the batch's stream
         tbatch._check(lib.pu_batch_profile(tbatch._b, 1), "pu_batch_profile")
         for _ in range(n_ev):
@@ -1076,7 +1158,7 @@ def bench_trees(args, cfg, world, rank, local_rank, dev):
             extra["rccl_world"] = chk["rccl_world"]
             extra["lnl_rel_err_vs_cpu"] = max(chk["lnl_rel_err_vs_cpu"],
                                               chk["sitewise_max_rel_err_vs_cpu"])
-    return dict({
+    res = dict({
         "metric": METRIC, "value": round(value, 3), "unit": "M updates/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True,
@@ -1100,6 +1182,9 @@ def bench_trees(args, cfg, world, rank, local_rank, dev):
         "roofline": roofline,
         "lnl_max_rel_diff_vs_sync_runs": max_rel,
     }, **extra)
+    if roofline is None:
+        del res["roofline"]
+    return res
 
 
 def bench_edges(tm, model, rm, codes, K, C, S, ntax, args, cfg):
@@ -1158,6 +1243,11 @@ def bench_edges(tm, model, rm, codes, K, C, S, ntax, args, cfg):
         dn_runs += 1
     l_end, e_end = newton_stats()
     dn_launch, dn_evals = l_end - l_start, e_end - e_start
+    if args.dump_outputs:
+        # the last pu_edge_derivs call's (lnL, dlnL/dt, d2lnL/dt2) and the last
+        # pu_optimise_edge call's (length, lnL)
+        dump_outputs(args.dump_outputs, 0, 1,
+                     {"edge_derivs": out, "newton_edge": np.array([out_t.value, out_l.value])})
 
     # (r06) the reference's own minimisers (brent / dbrent, src/optimisation.pyx) through
     # pu_minimise_edge, over [1e-8, 10] from the same starting lengths: the device driver (one
@@ -1316,6 +1406,14 @@ def bench_patterns(args, dev):
     cnt = d_counts[:Uv].cpu().numpy()
     inv = d_inv.cpu().numpy()
     assert cnt.sum() == S and inv.min() == 0 and inv.max() == Uv - 1
+    if args.dump_outputs:
+        # counts and inverse index whole; the unique columns as a fixed seeded sample of patterns
+        pick = np.sort(np.random.default_rng(20240229).choice(Uv, size=min(Uv, 1500),
+                                                              replace=False))
+        cols = d_unique.view(nt, ld)[:, torch.from_numpy(pick).to(dev)].T.cpu().numpy()
+        dump_outputs(args.dump_outputs, 0, 1,
+                     {"n_patterns": np.array([Uv]), "counts": cnt, "inverse": inv,
+                      "unique_sample": cols})
     res = {
         "metric": "alignment columns compressed per second (np.unique(axis=1) with inverse "
                   "and counts, alignment.py:40-57); SURVEY 8(f) N2",

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 B=${B:-old}
 run() {  # label, then env assignments
   local label=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --config ${CFG:-cfg3} --steps ${STEPS:-200} --warmup 20 \
+  env "$@" timeout -k 10 300 python bench.py --full --config ${CFG:-cfg3} --steps ${STEPS:-200} --warmup 20 \
       --no-cpu-baseline $BENCH_ARGS > gpurun_out/ab_line.json 2> gpurun_out/ab_err.txt
   local rc=$?
   if [ $rc -ne 0 ]; then echo "$label rc=$rc"; tail -5 gpurun_out/ab_err.txt; exit $rc; fi

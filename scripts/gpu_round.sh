@@ -39,7 +39,7 @@ if [ -n "$PROFILE" ]; then
   fi
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  step bench 600 python bench.py --config $CFG --steps ${BENCH_STEPS:-200} --warmup 20 $BENCH_ARGS \
+  step bench 600 python bench.py --full --config $CFG --steps ${BENCH_STEPS:-200} --warmup 20 $BENCH_ARGS \
        > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
   cat gpurun_out/bench_$TAG.json; tail -4 gpurun_out/bench_$TAG.err
 fi

@@ -178,6 +178,39 @@ def test_roofline_lnl_only_is_issue_bound():
     json.dumps(r)
 
 
+def test_dump_outputs_writes_float64_within_the_budget(tmp_path):
+    """--dump-outputs: every array as float64 <name>.npy; an array over its share of the 64 MB
+    is cut to the same seeded sample of its rows every time (ascending row order); a rank of a
+    multi-rank run writes files of its own."""
+    big = np.arange(3_000_000, dtype=np.int64).reshape(-1, 3)  # 24 MB as float64
+    arrs = {"lnl": np.float64(-1.5), "small": np.arange(7, dtype=np.int32), "big": big,
+            "b2": big, "b3": big}
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, arrs)
+    bench.dump_outputs(str(tmp_path / "b"), 0, 1, arrs)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["b2.npy", "b3.npy", "big.npy", "lnl.npy", "small.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64_000_000
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in files}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["lnl"].tolist() == [-1.5] and got["small"].tolist() == list(range(7))
+    rows = got["big"]
+    assert rows.shape[1] == 3 and 0 < rows.shape[0] < big.shape[0]
+    assert np.all(np.diff(rows[:, 0]) > 0) and np.all(rows[:, 1] == rows[:, 0] + 1)
+    for f in files:
+        np.testing.assert_array_equal(got[f[:-4]], np.load(str(tmp_path / "b" / f)))
+    bench.dump_outputs(str(tmp_path / "c"), 1, 2, {"lnl": np.zeros(1)})
+    assert os.listdir(str(tmp_path / "c")) == ["lnl.rank1.npy"]
+
+
+def test_plain_run_options_need_full():
+    """--events timed belongs to the roofline leg: refused without --full, before any device
+    work; --steps 0 is refused too."""
+    for argv, msg in ((["--events", "timed"], "--full"), (["--steps", "0"], "--steps")):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + argv, cwd=ROOT,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr
+
+
 def test_sweep_neighbour_check_flags_a_dip():
     """scripts/sweep.py's guard: a size whose per-update rate is more
     than 5 % below the better of its neighbours is flagged; a smooth curve passes."""
