@@ -18,7 +18,9 @@
  *     thread-safe (one host thread per context);
  *   - layouts are the reference's C-contiguous fp64 layouts:
  *       partials [site][category][state], scalers [site][category],
- *       P matrices [category][parent state][child state].
+ *       P matrices [category][parent state][child state];
+ *   - state rows (the simulator) are uint8 [row][site], one state index in [0, K) per byte,
+ *     row-major with a row stride in bytes; a row is a tip slot or a node.
  */
 #ifndef PHYLO_HIP_H
 #define PHYLO_HIP_H
@@ -262,6 +264,49 @@ int pu_compress_patterns_device(int device, void *stream, const uint8_t *d_codes
                                 int64_t n_sites, int n_codes, uint8_t *d_unique,
                                 int64_t ld_unique, int64_t *d_counts, int64_t *d_inverse,
                                 int64_t *n_unique_out);
+
+/* ---- simulation down the tree (the reference's src/simulation.pyx) -------------------- */
+/* Replaces set_seed / weighted_choice(s) / evolve_states (src/simulation.pyx:13-19, 22-60,
+ * 63-87).  The reference draws from libc rand(), one sequential stream; here every draw has
+ * an address -- (seed, global site g, draw d) -- and is a pure function of it:
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (g lo, g hi, d, 0), key = (seed lo, seed hi)),
+ *   u = ((x1 >> 5) * 2^26 + (x0 >> 6)) * 2^-53 in [0, 1);
+ *   pick(w[0..n), u): cum_j = cum_{j-1} + w_j (fp64 adds in index order), r = u * cum_{n-1},
+ *   the first j with cum_j > r, else n - 1 (weighted_choice's comparison, :35-41; the
+ *   reference returns 0 in that unreachable-in-practice case).
+ * So results do not depend on the launch, the chunking, the op order or the site range of the
+ * call: column g is the same in every call that covers it. */
+/* src/simulation.pyx:63-87 evolve_states over one branch: child[s] = pick(probs[rate_class[s]]
+ * [parent[s]][.], u(seed, first_site + s, draw)); probs [C][K][K] (the project layout; the
+ * reference's is [K][K][C]).  K, C <= 256; rate_class may be NULL when C = 1.  PU_E_ARG:
+ * n_sites <= 0, first_site < 0, a null buffer, a parent state >= K or a class >= C. */
+int pu_evolve_states(int device, int n_states, int n_cat, int64_t n_sites, uint64_t seed,
+                     int64_t first_site, uint32_t draw, const double *probs,
+                     const uint8_t *parent_states, const uint8_t *rate_class,
+                     uint8_t *child_states_out);
+/* evolve_states down the whole tree (src/simulation.pyx:63-87 per branch, driven in the
+ * reference by the caller's loop over the tree): ctx's current schedule oriented away from
+ * root_a, its current lengths (those pu_get_branch_lengths returns, after pu_optimise_* /
+ * pu_minimise_edge too) and model.  Site g = first_site + column draws d = 0: its rate category,
+ * pick(weights); d = 1: the state of root_a, pick(freqs); d = 2 + v: the state of every other
+ * node v, pick(P_v[category][state of v's parent][.]), P_v = P(len_v * rate) and root_b hanging
+ * from root_a with root_len.  P comes from the model's eigen-system on the device, or -- on a
+ * context on host matrices (pu_set_model_p) -- from its pu_pmat_provider (order 0).  Needs no
+ * tip data beyond the tip declarations the schedule required and changes no result of the
+ * context.  tips_out [n_tips][n_sites] in tip-slot order; nullable: cats_out [n_sites],
+ * nodes_out [n_nodes][n_sites] (every node's state), cum_out [n_nodes][C][K][K] (the cumulative
+ * rows the draws used: row v is the edge above v, row root_a is zero).  Sites are processed
+ * in chunks (a node-major uint8 workspace of at most 256 MiB; PU_SIM_CHUNK=<sites>, read at each
+ * call, overrides the chunk).  PU_E_STATE: before pu_set_model* / pu_set_schedule, or host
+ * matrices without a provider; PU_E_ARG: n_sites <= 0, first_site < 0, null tips_out. */
+int pu_simulate(pu_ctx *ctx, uint64_t seed, int64_t first_site, int64_t n_sites,
+                uint8_t *tips_out, uint8_t *cats_out, uint8_t *nodes_out, double *cum_out);
+/* The same into device buffers on the context's stream, rows ld bytes apart (ld >= n_sites,
+ * ld_nodes >= n_sites, else PU_E_ARG), ready for pu_compress_patterns_device; asynchronous
+ * (a repeated call on an unchanged tree only queues kernels).  d_cats, d_nodes nullable. */
+int pu_simulate_device(pu_ctx *ctx, uint64_t seed, int64_t first_site, int64_t n_sites,
+                       uint8_t *d_tips, int64_t ld, uint8_t *d_cats, uint8_t *d_nodes,
+                       int64_t ld_nodes);
 
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.

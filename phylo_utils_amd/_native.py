@@ -25,6 +25,8 @@ PU_OWN_STREAM = ctypes.c_void_p(-1)
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
+_c_u64 = ctypes.c_uint64
+_c_u32 = ctypes.c_uint32
 _c_dbl = ctypes.c_double
 _P = ctypes.c_void_p
 
@@ -91,6 +93,10 @@ SIGNATURES = {
     "pu_compress_patterns": (_c_int, [_c_int, _P, _c_int, _c_i64, _c_int, _P, _P, _P, _P]),
     "pu_compress_patterns_device": (_c_int, [_c_int, _P, _P, _c_int, _c_i64, _c_int, _P,
                                              _c_i64, _P, _P, _P]),
+    "pu_evolve_states": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _c_u64, _c_i64, _c_u32, _P, _P,
+                                  _P, _P]),
+    "pu_simulate": (_c_int, [_P, _c_u64, _c_i64, _c_i64, _P, _P, _P, _P]),
+    "pu_simulate_device": (_c_int, [_P, _c_u64, _c_i64, _c_i64, _P, _c_i64, _P, _P, _c_i64]),
     "pu_ctx_stream": (_P, [_P]),
     "pu_ctx_device_bytes": (_c_i64, [_P]),
     "pu_write_ceiling": (_c_int, [_c_int, _c_i64, _c_int, _P]),

@@ -85,6 +85,8 @@ struct TipStore {
     }
 };
 
+struct SimState;  // pu_simulate.hip: the simulator's device buffers of a context
+
 }  // namespace pu
 
 struct pu_ctx {
@@ -220,6 +222,9 @@ struct pu_ctx {
     double *d_asc_corr = nullptr;
     std::vector<double> h_pattern_w;  // host copy of the pattern weights
 
+    // alignment simulation (pu_simulate.hip): allocated at the first pu_simulate* call
+    pu::SimState *sim = nullptr;
+
     // profiling: event triples per recorded run
     bool profile = false;
     std::vector<hipEvent_t> ev;
@@ -254,6 +259,8 @@ int refresh_host_p(pu_ctx *c);
 int ensure_host_p(pu_ctx *c);
 // pu_edge.cpp: release the edge-operation buffers of a context
 void edge_free(pu_ctx *c);
+// pu_simulate.hip: release the simulator's buffers of a context
+void sim_free(pu_ctx *c);
 // enqueue the ascertainment-bias correction of site_lnl and *lnl (no-op when off)
 int enqueue_ascbias(pu_ctx *c, double *lnl);
 // stateless seam calls (pu_clv, pu_lnl_node, pu_lnl_branch*): one scratch buffer and stream

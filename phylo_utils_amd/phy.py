@@ -19,7 +19,10 @@ two of ``+F{freqs}`` and ``+G<ncat>{alpha}``.  Differences, all deliberate:
   ``alignment.read_fasta``).
 Extensions: ``--optimise`` runs branch-length optimisation passes on the GPU first
 (``--optimiser newton|brent|dbrent``)
-(SURVEY 8(f) N1); ``--ascertainment`` applies the Lewis correction (N3); ``--device``.
+(SURVEY 8(f) N1); ``--ascertainment`` applies the Lewis correction (N3); ``--device``;
+``--simulate N [--seed S] [-o out.fasta]`` needs no ``-s``: it simulates N columns down the
+tree under the model on the GPU (``phylo_utils_amd.simulation``, the reference's
+``src/simulation.pyx``) and writes them as FASTA, to stdout without ``-o``.
 """
 from __future__ import annotations
 
@@ -132,6 +135,11 @@ def parse_cli(argv=None):
                          "src/optimisation.pyx minimisers)")
     ap.add_argument("--ascertainment", choices=["reference", "weighted"], default=None,
                     help="Lewis ascertainment-bias correction")
+    ap.add_argument("--simulate", type=int, default=None, metavar="N",
+                    help="simulate N alignment columns down the tree (no -s) and write FASTA")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --simulate")
+    ap.add_argument("-o", "--output", type=str, default=None,
+                    help="FASTA file of --simulate (default: stdout)")
     return ap.parse_args(argv)
 
 
@@ -139,6 +147,12 @@ def validate_args(args):
     """bin/phy.py:22-30."""
     if args.tree is None:
         raise ValueError("Tree file not specified")
+    if getattr(args, "simulate", None) is not None:
+        if args.simulate <= 0:
+            raise ValueError("--simulate needs a positive number of sites")
+        if not os.path.exists(args.tree):
+            raise FileNotFoundError("Tree file {} does not exist".format(args.tree))
+        return
     if args.alignment is None:
         raise ValueError("Alignment file not specified")
     if not os.path.exists(args.tree):
@@ -169,6 +183,28 @@ def run(args, out=None):
     return lnl
 
 
+def run_simulate(args, out=None):
+    """--simulate: FASTA of args.simulate columns down the tree under the model string."""
+    from .simulation import simulate_alignment, states_to_sequences
+    with open(args.tree) as fh:
+        tree = parse_newick(fh.read())
+    desc = parse_model_string(args.model)
+    alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
+    names, states = simulate_alignment(tree, build_model(desc), build_rate_model(desc),
+                                       args.simulate, seed=args.seed, device=args.device)
+    seqs = states_to_sequences(states, alphabet)
+    fh = open(args.output, "w") if args.output else (sys.stdout if out is None else out)
+    try:
+        for name, seq in zip(names, seqs):
+            fh.write(">{}\n".format(name))
+            for i in range(0, len(seq), 60):
+                fh.write(seq[i:i + 60] + "\n")
+    finally:
+        if args.output:
+            fh.close()
+    return names, states
+
+
 def main(argv=None):
     args = parse_cli(argv)
     try:
@@ -177,7 +213,10 @@ def main(argv=None):
         sys.stderr.write("ERROR: {}\n".format(e))
         return 1
     try:
-        run(args)
+        if args.simulate is not None:
+            run_simulate(args)
+        else:
+            run(args)
     except ValueError as e:
         sys.stderr.write("ERROR: {}\n".format(e))
         return 1

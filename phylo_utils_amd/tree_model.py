@@ -581,6 +581,30 @@ class TreeModel(object):
         self._pull_lengths()
         return self._lnl
 
+    # ------------------------------------------------------------------ simulation
+    def simulate(self, n_sites, seed=0, first_site=0, return_categories=False,
+                 return_ancestral=False, return_cum=False):
+        """Simulate `n_sites` alignment columns down this model's tree on its own context
+        (pu_simulate; the reference's src/simulation.pyx evolve_states per branch): the
+        current topology, branch lengths -- after optimise_edge / optimise_branch_lengths too,
+        with no re-upload -- and models.  Returns the states uint8 [n_taxa][n_sites], rows in
+        `self.names` order; with any of the flags a tuple (states[, categories [n_sites]]
+        [, states of every node [n_nodes][n_sites]][, the cumulative rows the draws used
+        [n_nodes][C][K][K]]).  Column j is global site first_site + j and depends only on the
+        seed and that number (phylo_utils_amd.simulation).  The resident partials, the lnL and
+        the model's state are left as they are."""
+        if self._ctx is None:
+            raise ValueError("initialise first")
+        from .simulation import simulate_on_context
+        n_nodes, n_leaves, _, C, K = self._ctx_shape
+        res = simulate_on_context(self._ctx, n_leaves, n_nodes, C, K, n_sites, seed, first_site,
+                                  return_categories, return_ancestral, return_cum)
+        rows = np.array([self.names[n] for n in self._slot_names])
+        states = np.empty_like(res["tips"])
+        states[rows] = res["tips"]
+        extra = [res[k] for k in ("cats", "nodes", "cum") if k in res]
+        return (states,) + tuple(extra) if extra else states
+
     # ------------------------------------------------------------------ outputs
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
