@@ -308,6 +308,70 @@ int pu_simulate_device(pu_ctx *ctx, uint64_t seed, int64_t first_site, int64_t n
                        uint8_t *d_tips, int64_t ld, uint8_t *d_cats, uint8_t *d_nodes,
                        int64_t ld_nodes);
 
+/* ---- pairwise ML distances (the reference's phylo_utils/likelihood.py:226-236) --------- */
+/* Replaces optimise(model, partials_a, partials_b, min_brlen, max_brlen) (likelihood.py:226-236,
+ * with brent_optimise / scipy_optimise beside it), which returns (t, -1 / lnL''(t)) for two
+ * sequences, for every requested pair of a coded alignment at once, with no context (DESIGN
+ * 4.11, normative).  codes: uint8 [n_taxa][n_sites], row-major, each < n_codes <= 32, rows of
+ * code_table [n_codes][K]; site_weights [n_sites] (NULL: 1; pattern counts after compression).
+ * pairs [n_pairs][2] taxon indices in any order, repeats allowed; NULL: all i < j in row-major
+ * order, and n_pairs must then be n_taxa (n_taxa - 1) / 2.
+ *   lnL_ab(t) = sum_{u,v} N_ab[u][v] log F_uv(t), N_ab[u][v] = sum_s w_s [a_s = u][b_s = v],
+ *   F_uv(t) = sum_m L[u][m] R[v][m] g_m(t), L[u][m] = sum_i pi_i x_u[i] evecs[i][m],
+ *   R[v][m] = sum_j ivecs[m][j] x_v[j], g_m(t) = sum_c q_c exp(evals_m r_c t); derivatives in t
+ *   with the factor r_c included, as pu_edge_derivs; F' = F'' = 0 for a bin whose code u or v
+ *   has a constant tip vector (a gap: F does not depend on t).
+ * Pairs are processed in chunks (count matrices and their per-segment slabs within 256 MiB;
+ * PU_DIST_CHUNK=<pairs>, read at each call, lowers the chunk); no result depends on the chunk.
+ * PU_E_ARG, before any device is touched: a null buffer, n_taxa < 2, n_sites <= 0, n_codes
+ * outside [1, 32], n_states not 2, 4 or 20, n_cat outside [1, PU_PAIR_MAX_CAT] (the kernel
+ * keeps rates and weights in LDS), !(0 < lo < hi), tol <= 0, max_iter < 0, a pair index out of
+ * range or i == j, n_pairs < 1, ld < n_sites, a t0 outside [lo, hi], and -- host forms -- a code
+ * >= n_codes. */
+#define PU_PAIR_MAX_CAT 64
+/* likelihood.py:226-236's sufficient statistic: counts_out [n_pairs][n_codes][n_codes], the
+ * weighted pair count matrices N_ab (row: the code of the pair's first taxon).  A bin's adds run
+ * in site order within a segment of the sites and the segments are added in order; the
+ * segmentation depends on n_sites alone.  With integer weights the counts are exact. */
+int pu_pair_counts(int device, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes,
+                   const double *site_weights, int64_t n_pairs, const int32_t *pairs,
+                   double *counts_out);
+/* likelihood.py:226-236 for every pair: out5 [n_pairs][5] = {t, lnL(t), lnL'(t), lnL''(t),
+ * evaluations} -- the variance is -1 / lnL''(t).  A safeguarded Newton iteration on lnL'(t) = 0
+ * in [lo, hi], one wave per pair in one launch per chunk: lnL'(lo) <= 0 gives t = lo (one
+ * evaluation; a pair without an informative site lands here with zero derivatives), lnL'(hi)
+ * >= 0 gives t = hi (two); otherwise, from t0 (NULL, or not inside: sqrt(lo hi)), a bracket
+ * lnL'(a) > 0 > lnL'(b) is kept, the Newton step is taken when lnL'' < 0 and it stays inside the
+ * bracket, else the bracket is halved; a step below tol is taken and the result evaluated where
+ * it lands; after max_iter iterations without such a step the last evaluated point is returned
+ * (evaluations = 2 + max_iter: not converged).  max_iter = 0: one evaluation at t0.  A bin with
+ * N > 0 and F <= 0 gives lnL = -inf and t = lnL' = lnL'' = NaN.  Results are bitwise repeatable. */
+int pu_pair_distances(int device, int n_states, int n_cat, int n_codes, const double *code_table,
+                      const double *evecs, const double *evals, const double *ivecs,
+                      const double *freqs, const double *rates, const double *cat_weights,
+                      const uint8_t *codes, int n_taxa, int64_t n_sites,
+                      const double *site_weights, int64_t n_pairs, const int32_t *pairs,
+                      const double *t0, double lo, double hi, double tol, int max_iter,
+                      double *out5);
+/* likelihood.py:226-236 on device buffers -- the output of pu_simulate_device or
+ * pu_compress_patterns_device with no copy: d_codes rows ld bytes apart (ld >= n_sites),
+ * d_site_weights (nullable) and d_out5 in device memory; the model, pairs and t0 are host
+ * buffers, copied before the call returns.  Asynchronous on the caller's stream (hipStream_t as
+ * void*).  Precondition: every code < n_codes (a larger code is counted nowhere). */
+int pu_pair_distances_device(int device, void *stream, int n_states, int n_cat, int n_codes,
+                             const double *code_table, const double *evecs, const double *evals,
+                             const double *ivecs, const double *freqs, const double *rates,
+                             const double *cat_weights, const uint8_t *d_codes, int64_t ld,
+                             int n_taxa, int64_t n_sites, const double *d_site_weights,
+                             int64_t n_pairs, const int32_t *pairs, const double *t0, double lo,
+                             double hi, double tol, int max_iter, double *d_out5);
+/* Event timing of the pair kernels (scripts/time_distances.py): with pu_pair_profile(device, 1)
+ * every pair call records events around its launches; pu_pair_kernel_ms waits for the last
+ * call's and returns the time of its count launches (k_pair_counts and the slab merge) and of
+ * its k_pair_newton launches, in ms, summed over the chunks. */
+int pu_pair_profile(int device, int on);
+int pu_pair_kernel_ms(int device, double *counts_ms, double *newton_ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -22,7 +22,10 @@ Extensions: ``--optimise`` runs branch-length optimisation passes on the GPU fir
 (SURVEY 8(f) N1); ``--ascertainment`` applies the Lewis correction (N3); ``--device``;
 ``--simulate N [--seed S] [-o out.fasta]`` needs no ``-s``: it simulates N columns down the
 tree under the model on the GPU (``phylo_utils_amd.simulation``, the reference's
-``src/simulation.pyx``) and writes them as FASTA, to stdout without ``-o``.
+``src/simulation.pyx``) and writes them as FASTA, to stdout without ``-o``;
+``-s aln.fasta -m MODEL --distances [-o FILE]`` needs no ``-t``: it writes the square PHYLIP
+matrix of the pairwise ML distances (``phylo_utils_amd.distance``, the reference's
+``likelihood.py:226-236`` per pair), names in alignment order, ``%.10g``.
 """
 from __future__ import annotations
 
@@ -138,13 +141,23 @@ def parse_cli(argv=None):
     ap.add_argument("--simulate", type=int, default=None, metavar="N",
                     help="simulate N alignment columns down the tree (no -s) and write FASTA")
     ap.add_argument("--seed", type=int, default=0, help="seed of --simulate")
+    ap.add_argument("--distances", action="store_true",
+                    help="write the PHYLIP matrix of pairwise ML distances of -s (no -t)")
     ap.add_argument("-o", "--output", type=str, default=None,
-                    help="FASTA file of --simulate (default: stdout)")
+                    help="output file of --simulate / --distances (default: stdout)")
     return ap.parse_args(argv)
 
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "distances", False):
+        if getattr(args, "simulate", None) is not None:
+            raise ValueError("--distances and --simulate exclude each other")
+        if args.alignment is None:
+            raise ValueError("Alignment file not specified")
+        if not os.path.exists(args.alignment):
+            raise FileNotFoundError("Alignment file {} does not exist".format(args.alignment))
+        return
     if args.tree is None:
         raise ValueError("Tree file not specified")
     if getattr(args, "simulate", None) is not None:
@@ -205,6 +218,23 @@ def run_simulate(args, out=None):
     return names, states
 
 
+def run_distances(args, out=None):
+    """--distances: the PHYLIP matrix of the alignment's pairwise ML distances."""
+    from .distance import pairwise_distances, write_phylip
+    aln = A.read_fasta(args.alignment)
+    desc = parse_model_string(args.model)
+    alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
+    names, D, V = pairwise_distances(aln, build_model(desc), build_rate_model(desc), alphabet,
+                                     device=args.device)
+    fh = open(args.output, "w") if args.output else (sys.stdout if out is None else out)
+    try:
+        write_phylip(names, D, fh)
+    finally:
+        if args.output:
+            fh.close()
+    return names, D, V
+
+
 def main(argv=None):
     args = parse_cli(argv)
     try:
@@ -213,7 +243,9 @@ def main(argv=None):
         sys.stderr.write("ERROR: {}\n".format(e))
         return 1
     try:
-        if args.simulate is not None:
+        if args.distances:
+            run_distances(args)
+        elif args.simulate is not None:
             run_simulate(args)
         else:
             run(args)

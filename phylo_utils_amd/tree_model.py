@@ -606,6 +606,27 @@ class TreeModel(object):
         return (states,) + tuple(extra) if extra else states
 
     # ------------------------------------------------------------------ outputs
+    def pairwise_distances(self, **kw):
+        """ML distances and variances of all pairs of the model's own alignment under its
+        substitution and rate models (``distance.pairwise_distances``; the reference's
+        phylo_utils/likelihood.py:226-236 per pair): (names in alignment order, D, V).  Needs no
+        tree and does not touch the context."""
+        from . import distance
+        if self.alignment is None:
+            raise ValueError("No alignment has been set")
+        names = sorted(self.names, key=self.names.get)
+        if getattr(self, "_codes", None) is not None:
+            codes, table = self._codes
+        else:
+            coded = partials_to_codes(np.asarray(self.alignment))
+            if coded is None or len(coded[1]) > 32:
+                raise ValueError("pairwise distances need tips of at most 32 distinct vectors")
+            codes, table = coded
+        kw.setdefault("device", self.device)
+        kw.setdefault("weights", np.asarray(self.siteweights, dtype=np.float64))
+        return distance.pairwise_distances((codes, table, names), self.substitution_model,
+                                           getattr(self, "rate_model", None), **kw)
+
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
         self._ensure()
