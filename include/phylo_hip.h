@@ -71,7 +71,12 @@ int pu_discrete_gamma(double alpha, int n_cat, int median_rates, double *rates_o
 
 /* ---- TreeModel-equivalent context ---------------------------------------------------- */
 /* TreeModel.initialise allocation, tree_model.py:101-124.  n_nodes = 2N-2 node
- * indices as numbered by Traversal (traversal.py:16-21); n_patterns = S. */
+ * indices as numbered by Traversal (traversal.py:16-21); n_patterns = S.
+ * 1 <= n_cat <= 64, otherwise PU_E_ARG.  The traversal (pu_run) runs every n_cat up to 64
+ * for n_states 2, 4 and 20.  The edge operations keep their matrices in the LDS of one
+ * workgroup (160 KiB) and return PU_E_ARG, before any launch, above: pu_edge_derivs and the
+ * optimisers n_cat 64 / 60 / 10 for n_states 2 / 4 / 20; pu_edge_lnl 64 / 64 / 21;
+ * pu_update_partials 64 / 64 / 23.  The context stays usable after such a refusal. */
 int pu_ctx_create(pu_ctx **out, int device, int n_nodes, int n_tips, int64_t n_patterns,
                   int n_cat, int n_states, int flags);
 void pu_ctx_destroy(pu_ctx *ctx);

@@ -6,7 +6,8 @@ Mirrors ``phylo_utils/alignment/`` (``alignment.py:26-66``, ``charmaps.py``,
 * ``DNA``, ``PROTEIN``, ``BINARY`` alphabet constants (``alphabets.py:1-3``);
   ``seq_to_partials`` also accepts the names ``"dna"``/``"protein"``/``"binary"``.
 * charmaps: IUPAC nucleotide ambiguity (gap, N = all states), the 20 amino
-  acids plus ``- ? X`` (all states), binary ``0 1 - N``; upper and lower case.
+  acids plus ``- ? X`` (all states), binary ``0 1 - N`` (and ``?``, read as ``-``); upper
+  and lower case.
 * ``alignment_to_numpy`` compresses identical columns with
   ``np.unique(axis=1, return_inverse, return_counts)`` exactly as the reference
   (patterns come out in lexicographic order).
@@ -55,6 +56,12 @@ protein_charmap = _build_charmap(PROTEIN_STATES, {s: s for s in PROTEIN_STATES},
 binary_charmap = {"-": [1.0, 1.0], "N": [1.0, 1.0], "0": [1.0, 0.0], "1": [0.0, 1.0]}
 
 CHARMAPS = {DNA: dna_charmap, PROTEIN: protein_charmap, BINARY: binary_charmap}
+# A deliberate departure from the reference: characters accepted beyond the reference's charmap,
+# each read as another character of it.  Morphological matrices write the unknown state as "?",
+# which the reference's binary charmap ("0 1 - N") refuses.  CHARMAPS stays the reference's,
+# key for key; the complete accepted set (charmap keys plus these) is pinned by
+# tests/test_host.py::test_accepted_characters_per_alphabet.
+ALIASES = {BINARY: {"?": "-"}}
 NSTATES = {DNA: 4, PROTEIN: 20, BINARY: 2}
 
 
@@ -72,8 +79,9 @@ def seq_to_partials(seq, alphabet):
     cmap = CHARMAPS.get(alphabet_code(alphabet))
     if cmap is None:
         raise ValueError("unknown alphabet %r" % alphabet)
+    alias = ALIASES.get(alphabet_code(alphabet), {})
     try:
-        return np.ascontiguousarray([cmap[ch] for ch in seq], dtype=np.float64)
+        return np.ascontiguousarray([cmap[alias.get(ch, ch)] for ch in seq], dtype=np.float64)
     except KeyError as e:
         raise ValueError("character %s is not in the alphabet" % e)
 
@@ -121,6 +129,8 @@ def code_table(alphabet):
     lut = np.full(256, 255, dtype=np.uint8)
     for c, k in zip(chars, np.asarray(inv).reshape(-1)):
         lut[ord(c)] = k
+    for c, same in ALIASES.get(alphabet_code(alphabet), {}).items():
+        lut[ord(c)] = lut[ord(same)]
     return np.ascontiguousarray(table), lut
 
 

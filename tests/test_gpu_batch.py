@@ -78,9 +78,12 @@ def _oracle_lnl(orc, tm):
     return lnl
 
 
-@pytest.mark.parametrize("env", [{"PU_BATCH_GROUP": "0"}, {"PU_BATCH_GROUP": "4"},
-                                 {"PU_BATCH_GROUP": "8", "PU_BATCH_WAVES": "7"},
-                                 {"PU_BATCH_GROUP": "16", "PU_BATCH_WAVES": "1"}])
+GRID_ENVS = [{"PU_BATCH_GROUP": "0"}, {"PU_BATCH_GROUP": "4"},
+             {"PU_BATCH_GROUP": "8", "PU_BATCH_WAVES": "7"},
+             {"PU_BATCH_GROUP": "16", "PU_BATCH_WAVES": "1"}]
+
+
+@pytest.mark.parametrize("env", GRID_ENVS)
 def test_batch_grid_orders_bitwise(monkeypatch, env):
     """Every grid order of the batched traversal (tree-major, groups of g trees with a tile
     index's workgroups adjacent, the last group smaller) and both builds give each tree its

@@ -163,11 +163,19 @@ def test_engine_modes_agree(name, compact, keep, reorder):
     np.testing.assert_array_equal(tm.sitewise_patterns(), base.sitewise_patterns())
 
 
-@pytest.mark.parametrize("env", [{"PU_LDS_SLOTS": "0"}, {"PU_LDS_SLOTS": "1"},
-                                 {"PU_FORCE_GENERIC": "1"}, {"PU_KEEP_OCC": "6"},
-                                 {"PU_KEEP_OCC": "7"}, {"PU_CHUNK_USES": "3"},
-                                 {"PU_SPLIT": "1"}, {"PU_SPLIT": "2"}, {"PU_SPLIT": "8"},
-                                 {"PU_SPLIT": "4", "PU_LDS_SLOTS": "1", "PU_CHUNK_USES": "3"}])
+# the env lists of the bitwise build / plan tests (tests/test_gpu_twostate.py runs them on K = 2)
+PLAN_ENVS = [{"PU_LDS_SLOTS": "0"}, {"PU_LDS_SLOTS": "1"},
+             {"PU_FORCE_GENERIC": "1"}, {"PU_KEEP_OCC": "6"},
+             {"PU_KEEP_OCC": "7"}, {"PU_CHUNK_USES": "3"},
+             {"PU_SPLIT": "1"}, {"PU_SPLIT": "2"}, {"PU_SPLIT": "8"},
+             {"PU_SPLIT": "4", "PU_LDS_SLOTS": "1", "PU_CHUNK_USES": "3"}]
+RSLOT_ENVS = [{"PU_LDS_SLOTS": "3"}, {"PU_LDS_SLOTS": "5"}, {"PU_KEEP_OCC": "6"}]
+KEEP_OCC_ENVS = [{"PU_KEEP_OCC": "3"}, {"PU_KEEP_OCC": "5"},
+                 {"PU_KEEP_OCC": "6"}, {"PU_KEEP_OCC": "7"},
+                 {"PU_LDS_PAD": "17408"}, {"PU_SPLIT": "9"}]
+
+
+@pytest.mark.parametrize("env", PLAN_ENVS)
 @pytest.mark.parametrize("name", ["deep_scaling", "cfg3_small", "ambig_dna", "ambig_prot"])
 def test_kernel_builds_and_plans_bitwise_equal(monkeypatch, name, env):
     """Every k_prune build / plan computes each node with identical arithmetic: HBM
@@ -844,8 +852,7 @@ def test_lnl_only_tip_products_bitwise(monkeypatch, name):
 
 
 
-@pytest.mark.parametrize("env", [{"PU_LDS_SLOTS": "3"}, {"PU_LDS_SLOTS": "5"},
-                                 {"PU_KEEP_OCC": "6"}])
+@pytest.mark.parametrize("env", RSLOT_ENVS)
 def test_register_stash_slots_bitwise(monkeypatch, env):
     """A 500-taxon KEEP plan at 4 workgroups per CU overflows its 3 LDS stash slots; the
     occupancy plan keeps two more waiting parents in registers (TV_RSLOTS) instead of reading
@@ -895,9 +902,7 @@ def test_split_plans_with_dense_tips(monkeypatch, name):
         np.testing.assert_array_equal(tm.partials, p0)
 
 
-@pytest.mark.parametrize("env", [{"PU_KEEP_OCC": "3"}, {"PU_KEEP_OCC": "5"},
-                                 {"PU_KEEP_OCC": "6"}, {"PU_KEEP_OCC": "7"},
-                                 {"PU_LDS_PAD": "17408"}, {"PU_SPLIT": "9"}])
+@pytest.mark.parametrize("env", KEEP_OCC_ENVS)
 def test_keep_occupancy_rule_bitwise(monkeypatch, env):
     """DNA KEEP plans are occupancy plans (pu_set_schedule / keep_occupancy): k
     workgroups per CU, the most stash slots that fit, the build that allows k.  Every forced

@@ -12,6 +12,7 @@ import pytest
 from conftest import load_golden
 
 import sim_reference as R
+from twostate import TwoState
 from phylo_utils_amd import TreeModel, _native as N
 from phylo_utils_amd import alignment as A
 from phylo_utils_amd import phy, simulation
@@ -41,6 +42,7 @@ CASES = {
     "gtr50": lambda: (_tree(50, 50),) + gtr_g4(),
     "lg8": lambda: (_tree(8, 8), SM.LG(), GammaRateModel(4, 0.8)),
     "jc5": lambda: (_tree(5, 5), SM.JC69(), UniformRateModel()),
+    "two6": lambda: (_tree(6, 6), TwoState(0.3), GammaRateModel(4, 0.5)),
 }
 
 

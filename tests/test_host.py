@@ -127,6 +127,49 @@ def test_charmaps_match_reference(kind, alpha):
     np.testing.assert_array_equal(A.seq_to_partials(s, kind), [ref[c] for c in s])
 
 
+@pytest.mark.parametrize("kind,alpha,extra", [("dna", A.DNA, {}), ("protein", A.PROTEIN, {}),
+                                              ("binary", A.BINARY, {"?": "-"})])
+def test_accepted_characters_per_alphabet(kind, alpha, extra):
+    """The complete set of characters each alphabet accepts: the reference's charmap keys
+    (test_charmaps_match_reference) plus the documented extensions in alignment.ALIASES -- one,
+    a deliberate departure from the reference: the binary alphabet reads "?" as "-".  Both
+    ingest paths accept exactly that set and agree on every character: seq_to_partials (float
+    partials) and code_table's lut (codes into the table)."""
+    ref = golden_charmap(kind)
+    assert A.ALIASES.get(alpha, {}) == extra
+    assert not set(extra) & set(ref) and set(extra.values()) <= set(ref)
+    accepted = set(ref) | set(extra)
+    table, lut = A.code_table(alpha)
+    assert {chr(b) for b in range(256) if lut[b] != 255} == accepted
+    for b in range(256):
+        ch = chr(b)
+        if ch in accepted:
+            want = ref[extra.get(ch, ch)]
+            np.testing.assert_array_equal(A.seq_to_partials(ch, alpha)[0], want, err_msg=ch)
+            np.testing.assert_array_equal(table[lut[b]], want, err_msg=ch)
+        else:
+            with pytest.raises(ValueError):
+                A.seq_to_partials(ch, alpha)
+            with pytest.raises(ValueError):
+                A.char_codes([("a", ch)], alpha)
+    # the extension does not change the code table: it is the reference's distinct vectors
+    np.testing.assert_array_equal(table, np.unique(np.array(list(ref.values())), axis=0))
+
+
+def test_binary_question_mark_is_a_gap():
+    recs = [("a", "01?-N"), ("b", "?10N-")]
+    codes, table, names = A.char_codes(recs, A.BINARY)
+    np.testing.assert_array_equal(table[codes], np.stack([A.seq_to_partials(s, A.BINARY)
+                                                          for _, s in recs]))
+    np.testing.assert_array_equal(A.seq_to_partials("?", A.BINARY),
+                                  A.seq_to_partials("-", A.BINARY))
+    assert A.code_table(A.BINARY)[1][ord("?")] == A.code_table(A.BINARY)[1][ord("-")]
+    parts, w, inv, _ = A.alignment_to_numpy(recs, A.BINARY)
+    np.testing.assert_array_equal(parts[:, inv], table[codes])
+    with pytest.raises(ValueError):
+        A.seq_to_partials("?", A.DNA)
+
+
 def test_pattern_compression_like_reference():
     aln = [("a", "AACGTA-"), ("b", "AACGTAN"), ("c", "ATCGTAA")]
     parts, w, inv, names = A.alignment_to_numpy(aln, A.DNA)
