@@ -377,6 +377,48 @@ int pu_pair_distances_device(int device, void *stream, int n_states, int n_cat, 
 int pu_pair_profile(int device, int on);
 int pu_pair_kernel_ms(int device, double *counts_ms, double *newton_ms);
 
+/* ---- neighbour joining and BIONJ from a distance matrix (normative) -------- */
+/* A tree from a distance matrix, or one per matrix of a batch: classic neighbour joining
+ * (method 0; Saitou-Nei in the Studier-Keppler form) or BIONJ (method 1; Gascuel 1997, variances
+ * initialised to the distances).  D [n_mat][n][n], row-major; only the upper triangle is read
+ * and the diagonal is ignored.  Tips are clusters 0..n-1 and join m creates cluster n + m:
+ *   joins_out [n_mat][n-2][2]  the child ids of cluster n + m, smaller id first
+ *   lens_out  [n_mat][n-2][2]  their branch lengths, raw (they may be negative)
+ *   root_out  [n_mat][2], root_len_out [n_mat]  the root edge (2n-3, the last other cluster) and
+ *             its length: 2n-2 nodes with the root on an edge, the shape pu_set_schedule takes
+ *   q_out     [n_mat][n-3], nullable  the criterion Q of every chosen pair but the last
+ * While r > 3 clusters are live the pair a < b with the smallest Q_ab = (r-2) D_ab - R_a - R_b
+ * is joined (R: row sums, taken once in index order and updated after; ties to the
+ * lexicographically smallest (a, b)); the last three are joined without a criterion.  Every
+ * result is bitwise repeatable and does not depend on the tier.
+ * Tier A keeps the matrix in the LDS of one workgroup (n up to the n pu_nj_max_lds_n returns,
+ * one workgroup per matrix, one launch); tier B keeps it in device memory (two launches per
+ * join, all queued without a host read-back; matrices one after another).
+ * PU_NJ_TIER=A|B, read at each call, forces a tier where n allows it.
+ * PU_E_ARG, before any device is touched: a null buffer other than q_out, n < 3,
+ * n > PU_NJ_MAX_N (the working copies are n^2 doubles), n_mat < 1, method outside {0, 1},
+ * ld < n and -- host form -- a negative or non-finite entry of an upper triangle. */
+#define PU_NJ_MAX_N 8192
+int pu_nj(int device, int method, int n_mat, int n, const double *D, int32_t *joins_out,
+          double *lens_out, int32_t *root_out, double *root_len_out, double *q_out);
+/* The same on device buffers: matrix b starts at d_D + b n ld, its rows ld doubles apart
+ * (ld >= n); the outputs are device buffers.  Asynchronous on the caller's stream (hipStream_t
+ * as void*). */
+int pu_nj_device(int device, void *stream, int method, int n_mat, int n, const double *d_D,
+                 int64_t ld, int32_t *d_joins, double *d_lens, int32_t *d_root,
+                 double *d_root_len, double *d_q);
+/* The largest n whose matrix (method 1: matrices) fits the 160 KiB of LDS of one workgroup
+ * (tier A); host only. */
+int pu_nj_max_lds_n(int method);
+/* The t column of pu_pair_distances_device's rows d_out5 [n_pairs][5] as a matrix d_D (rows ld
+ * doubles apart, ld >= n_taxa), so that a distance run feeds pu_nj_device with no host copy.
+ * pairs NULL (n_pairs = n_taxa (n_taxa - 1) / 2, all i < j row-major): the whole symmetric
+ * matrix with a zero diagonal is written.  With a pair list (host buffer [n_pairs][2], copied
+ * before the call returns) both entries of every listed pair are written and nothing else.
+ * Asynchronous on the caller's stream.  PU_E_ARG as for the pair calls. */
+int pu_pair_matrix_device(int device, void *stream, int n_taxa, int64_t n_pairs,
+                          const int32_t *pairs, const double *d_out5, double *d_D, int64_t ld);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -106,6 +106,11 @@ SIGNATURES = {
                                           _c_dbl, _c_dbl, _c_dbl, _c_int, _P]),
     "pu_pair_profile": (_c_int, [_c_int, _c_int]),
     "pu_pair_kernel_ms": (_c_int, [_c_int, _P, _P]),
+    "pu_nj": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P]),
+    "pu_nj_device": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _P, _c_i64, _P, _P, _P, _P,
+                              _P]),
+    "pu_nj_max_lds_n": (_c_int, [_c_int]),
+    "pu_pair_matrix_device": (_c_int, [_c_int, _P, _c_int, _c_i64, _P, _P, _P, _c_i64]),
     "pu_ctx_stream": (_P, [_P]),
     "pu_ctx_device_bytes": (_c_i64, [_P]),
     "pu_write_ceiling": (_c_int, [_c_int, _c_i64, _c_int, _P]),

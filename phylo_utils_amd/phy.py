@@ -25,7 +25,11 @@ tree under the model on the GPU (``phylo_utils_amd.simulation``, the reference's
 ``src/simulation.pyx``) and writes them as FASTA, to stdout without ``-o``;
 ``-s aln.fasta -m MODEL --distances [-o FILE]`` needs no ``-t``: it writes the square PHYLIP
 matrix of the pairwise ML distances (``phylo_utils_amd.distance``, the reference's
-``likelihood.py:226-236`` per pair), names in alignment order, ``%.10g``.
+``likelihood.py:226-236`` per pair), names in alignment order, ``%.10g``;
+``-s aln.fasta -m MODEL --nj {nj,bionj} [-o tree.nwk]`` needs no ``-t`` either: the tree is the
+neighbour-joining (or BIONJ) tree of those distances (``phylo_utils_amd.nj``; the reference has
+no tree builder), written as Newick to ``-o`` when given, and the ``lnL = `` line is that tree's,
+after ``--optimise`` when asked.
 """
 from __future__ import annotations
 
@@ -143,13 +147,25 @@ def parse_cli(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of --simulate")
     ap.add_argument("--distances", action="store_true",
                     help="write the PHYLIP matrix of pairwise ML distances of -s (no -t)")
+    ap.add_argument("--nj", choices=["nj", "bionj"], default=None,
+                    help="take the tree from neighbour joining (or BIONJ) on the pairwise ML "
+                         "distances of -s (no -t); -o receives its Newick")
     ap.add_argument("-o", "--output", type=str, default=None,
-                    help="output file of --simulate / --distances (default: stdout)")
+                    help="output file of --simulate / --distances (default: stdout) / --nj")
     return ap.parse_args(argv)
 
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "nj", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None \
+                or args.tree is not None:
+            raise ValueError("--nj excludes --distances, --simulate and -t")
+        if args.alignment is None:
+            raise ValueError("Alignment file not specified")
+        if not os.path.exists(args.alignment):
+            raise FileNotFoundError("Alignment file {} does not exist".format(args.alignment))
+        return
     if getattr(args, "distances", False):
         if getattr(args, "simulate", None) is not None:
             raise ValueError("--distances and --simulate exclude each other")
@@ -176,16 +192,24 @@ def validate_args(args):
 
 def run(args, out=None):
     out = sys.stdout if out is None else out
-    with open(args.tree) as fh:
-        tree = parse_newick(fh.read())
+    nj = getattr(args, "nj", None)
+    if nj is None:
+        with open(args.tree) as fh:
+            tree = parse_newick(fh.read())
     aln = A.read_fasta(args.alignment)
     desc = parse_model_string(args.model)
     alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
     tm = TreeModel(device=args.device)
-    tm.set_tree(tree)
+    if nj is None:
+        tm.set_tree(tree)
     tm.set_alignment(aln, alphabet)
     tm.set_rate_model(build_rate_model(desc))
     tm.set_substitution_model(build_model(desc))
+    if nj is not None:  # --nj: the tree from the alignment's own distances
+        tree = tm.set_nj_tree(method=nj)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
     if args.ascertainment:
         tm.set_ascertainment_bias_correction(weighted=args.ascertainment == "weighted")
     tm.initialise()

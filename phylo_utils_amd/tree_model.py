@@ -627,6 +627,19 @@ class TreeModel(object):
         return distance.pairwise_distances((codes, table, names), self.substitution_model,
                                            getattr(self, "rate_model", None), **kw)
 
+    def set_nj_tree(self, method="nj", **distance_kw):
+        """A starting tree from the model's own data: ``pairwise_distances(**distance_kw)`` on
+        its alignment and models, then neighbour joining (`method` "nj" or "bionj",
+        ``nj.neighbour_joining``) on that matrix, then ``set_tree``.  Branch lengths below the
+        optimisers' lower bound 1e-8 (NJ lengths may be negative) are raised to it.  Needs what
+        the distances need: coded tips and a reversible model.  Returns the tree."""
+        from . import nj
+        names, D, _ = self.pairwise_distances(**distance_kw)
+        tree = nj.neighbour_joining(D, names, method=method, min_length=1e-8,
+                                    device=self.device)
+        self.set_tree(tree)
+        return tree
+
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
         self._ensure()
