@@ -419,6 +419,112 @@ int pu_nj_max_lds_n(int method);
 int pu_pair_matrix_device(int device, void *stream, int n_taxa, int64_t n_pairs,
                           const int32_t *pairs, const double *d_out5, double *d_D, int64_t ld);
 
+/* ---- bootstrap support of distance trees (normative) ------------------------ */
+/* The nonparametric bootstrap (Felsenstein 1985) of a neighbour-joining or BIONJ tree, with no
+ * host copy between its steps.  The resampling rule: S site patterns with non-negative integer
+ * weights w_s (fp64; NULL: all 1), N = sum_s w_s in [1, 2^31 - 1].  Replicate r -- a global
+ * number, r = first_rep + its row, so that a call continues a series -- draws N columns
+ * j = 0..N-1:
+ *   (x0, x1, ..) = philox4x32_10(counter = (j lo, j hi, r, 1), key = (seed lo, seed hi))
+ *   u = ((x1 >> 5) * 2^26 + (x0 >> 6)) * 2^-53     (the simulator's u; counter word 3 = 1)
+ *   c = min(floor(u * N), N - 1)                    (one fp64 multiply)
+ *   s = the first pattern whose inclusive integer prefix sum of w exceeds c;  W[r][s] += 1
+ * w_out uint32 [n_rep][n_sites]: every row sums to N, a pattern of weight 0 is never drawn, and
+ * a row depends on (seed, r, w) alone.
+ * PU_E_ARG, before any device is touched: a null output, n_rep < 1, n_sites < 1, replicate
+ * numbers outside [0, 2^32), N outside [1, 2^31 - 1] and -- host form -- a weight that is
+ * negative, non-integer or non-finite. */
+int pu_boot_weights(int device, uint64_t seed, int64_t first_rep, int n_rep, int64_t n_sites,
+                    const double *site_weights, uint32_t *w_out);
+/* The same on device buffers: d_site_weights (nullable) and d_w, its rows ldw words apart
+ * (ldw >= n_sites; the words between n_sites and ldw are left alone).  Asynchronous on the
+ * caller's stream (hipStream_t as void*).  Precondition: the device weights obey the rule (with
+ * N outside its range W is all zero). */
+int pu_boot_weights_device(int device, void *stream, uint64_t seed, int64_t first_rep, int n_rep,
+                           int64_t n_sites, const double *d_site_weights, uint32_t *d_w,
+                           int64_t ldw);
+/* The pair count matrices of every replicate in one pass over the alignment: counts_out
+ * [n_rep][n_pairs][n_codes][n_codes] fp64, N[r][p][u][v] = the sum of W[r][s] over the sites
+ * where pairs[p]'s first taxon shows code u and its second code v.  W uint32 [n_rep][n_sites];
+ * codes, pairs and n_codes as in pu_pair_counts.  The sums are integers: the result is exact,
+ * does not depend on the tiling, the segments or the chunks (PU_DIST_CHUNK caps the pairs of a
+ * chunk here too), and equals pu_pair_counts with site_weights = W[r] bit for bit.
+ * PU_E_ARG as for pu_pair_counts, and for n_rep < 1, a null W and a row of W whose sum is
+ * outside [1, 2^31 - 1]. */
+int pu_boot_pair_counts(int device, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes,
+                        const uint32_t *W, int n_rep, int64_t n_pairs, const int32_t *pairs,
+                        double *counts_out);
+/* pu_pair_distances for every replicate: out5_out [n_rep][n_pairs][5], the rows of replicate r
+ * bitwise equal to pu_pair_distances(..., site_weights = W[r], t0 = NULL, ...).  The counts of
+ * all replicates are taken in one pass (above) and all replicates x pairs go through the pair
+ * calls' Newton kernel as one list.  PU_E_ARG as for pu_pair_distances and pu_boot_pair_counts. */
+int pu_boot_distances(int device, int n_states, int n_cat, int n_codes, const double *code_table,
+                      const double *evecs, const double *evals, const double *ivecs,
+                      const double *freqs, const double *rates, const double *cat_weights,
+                      const uint8_t *codes, int n_taxa, int64_t n_sites, const uint32_t *W,
+                      int n_rep, int64_t n_pairs, const int32_t *pairs, double lo, double hi,
+                      double tol, int max_iter, double *out5_out);
+/* The same on device buffers (d_codes rows ld bytes apart, d_W rows ldw words apart, d_out5); the
+ * model and pairs are host buffers, copied before the call returns.  With d_D non-null (all
+ * pairs only: pairs NULL) the t column of every replicate is also written as the symmetric
+ * matrices d_D [n_rep][n_taxa][ldd] with a zero diagonal, the entries pu_pair_matrix_device
+ * writes, ready for pu_nj_device.  Asynchronous on the caller's stream. */
+int pu_boot_distances_device(int device, void *stream, int n_states, int n_cat, int n_codes,
+                             const double *code_table, const double *evecs, const double *evals,
+                             const double *ivecs, const double *freqs, const double *rates,
+                             const double *cat_weights, const uint8_t *d_codes, int64_t ld,
+                             int n_taxa, int64_t n_sites, const uint32_t *d_W, int64_t ldw,
+                             int n_rep, int64_t n_pairs, const int32_t *pairs, double lo, double hi,
+                             double tol, int max_iter, double *d_out5, double *d_D, int64_t ldd);
+/* Split support.  The reference and the n_rep replicates are trees in pu_nj's join form over
+ * the same n tips (ref_joins [n-2][2], ref_root [2]; joins [n_rep][n-2][2], roots [n_rep][2]).
+ * The nontrivial splits of a tree are the tip sets of its clusters n + m, m = 0..n-4 (cluster
+ * 2n-3 shares the root edge's split with root[1], or is trivial), each a bitset of
+ * ceil(n / 64) words, complemented when it holds tip 0.  support_out [n-3]: support[m] = the
+ * number of ok replicates whose tree holds a split equal, word for word, to the reference's
+ * split m, divided by n_ok; n_ok_out [1] = the number of replicates with ok[r] != 0 (ok int32
+ * [n_rep], NULL: all).  n_ok = 0 gives NaN.
+ * PU_E_ARG, before any device is touched: a null buffer other than ok, n < 3, n > PU_NJ_MAX_N,
+ * n_rep < 1 and -- host form -- a join of a cluster that is not live. */
+int pu_split_support(int device, int n, int n_rep, const int32_t *ref_joins,
+                     const int32_t *ref_root, const int32_t *joins, const int32_t *roots,
+                     const int32_t *ok, double *support_out, int32_t *n_ok_out);
+int pu_split_support_device(int device, void *stream, int n, int n_rep, const int32_t *d_ref_joins,
+                            const int32_t *d_ref_root, const int32_t *d_joins,
+                            const int32_t *d_roots, const int32_t *d_ok, double *d_support,
+                            int32_t *d_n_ok);
+/* The whole bootstrap on one stream, only the outputs coming back: the reference tree (method 0
+ * NJ, 1 BIONJ) of the distances under site_weights, then replicates 0..n_rep-1 of (seed,
+ * site_weights): their W, distances, matrices, ok[r] = every upper-triangle distance of
+ * replicate r is finite, trees and the support of the reference tree's splits over the ok
+ * replicates (a replicate with ok = 0 has an unspecified tree).  ref_*_out as pu_nj's outputs
+ * for one matrix, support_out [n-3], n_ok_out [1], rep_joins_out [n_rep][n-2][2] and
+ * rep_roots_out [n_rep][2] nullable.  Every result equals the composition of the separate calls
+ * above, pu_pair_distances, pu_pair_matrix_device and pu_nj, bit for bit.
+ * The call holds the out5 rows, matrices and join arrays of all replicates on the device at once,
+ * (1 + n_rep) (5 n (n - 1) / 2 + n^2 + 2 (n - 2) + 1) doubles, and W (n_rep n_sites words); only
+ * the count matrices are chunked.  Where that does not fit it returns PU_E_NOMEM, and the
+ * separate calls over ranges of replicates (first_rep) still run.  The split comparison is
+ * written for trees of up to a few hundred taxa (n^2 n_rep ceil(n / 64) word compares, no hash
+ * prefilter); it is correct, but has not been timed, in the thousands.
+ * PU_E_ARG: n_taxa < 3, and as for those calls. */
+int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes,
+                    const double *code_table, const double *evecs, const double *evals,
+                    const double *ivecs, const double *freqs, const double *rates,
+                    const double *cat_weights, const uint8_t *codes, int n_taxa, int64_t n_sites,
+                    const double *site_weights, uint64_t seed, int n_rep, double lo, double hi,
+                    double tol, int max_iter, int32_t *ref_joins_out, double *ref_lens_out,
+                    int32_t *ref_root_out, double *ref_root_len_out, double *support_out,
+                    int32_t *n_ok_out, int32_t *rep_joins_out, int32_t *rep_roots_out);
+/* Event timing of the two hot stages (scripts/time_bootstrap.py), as pu_pair_profile does for
+ * the pair calls: with pu_boot_profile(device, 1) every pu_boot_pair_counts / pu_boot_distances*
+ * call records events around its launches; pu_boot_kernel_ms waits for the last call's and
+ * returns the time of its count launches (k_boot_pair_counts and the slab merge) and of its
+ * k_pair_newton launches, in ms, summed over the chunks.  PU_BOOT_REP_CHUNK, read at each call,
+ * caps the replicates of a chunk as PU_DIST_CHUNK caps the pairs; no result depends on either. */
+int pu_boot_profile(int device, int on);
+int pu_boot_kernel_ms(int device, double *counts_ms, double *newton_ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -111,6 +111,25 @@ SIGNATURES = {
                               _P]),
     "pu_nj_max_lds_n": (_c_int, [_c_int]),
     "pu_pair_matrix_device": (_c_int, [_c_int, _P, _c_int, _c_i64, _P, _P, _P, _c_i64]),
+    "pu_boot_weights": (_c_int, [_c_int, _c_u64, _c_i64, _c_int, _c_i64, _P, _P]),
+    "pu_boot_weights_device": (_c_int, [_c_int, _P, _c_u64, _c_i64, _c_int, _c_i64, _P, _P,
+                                        _c_i64]),
+    "pu_boot_pair_counts": (_c_int, [_c_int, _P, _c_int, _c_i64, _c_int, _P, _c_int, _c_i64, _P,
+                                     _P]),
+    "pu_boot_distances": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _c_int, _c_i64, _P, _c_int, _c_i64, _P, _c_dbl, _c_dbl, _c_dbl,
+                                   _c_int, _P]),
+    "pu_boot_distances_device": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _c_i64, _c_int, _c_i64, _P, _c_i64, _c_int,
+                                          _c_i64, _P, _c_dbl, _c_dbl, _c_dbl, _c_int, _P, _P,
+                                          _c_i64]),
+    "pu_split_support": (_c_int, [_c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pu_split_support_device": (_c_int, [_c_int, _P, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pu_bootstrap_nj": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P,
+                                 _P, _P, _c_int, _c_i64, _P, _c_u64, _c_int, _c_dbl, _c_dbl,
+                                 _c_dbl, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pu_boot_profile": (_c_int, [_c_int, _c_int]),
+    "pu_boot_kernel_ms": (_c_int, [_c_int, _P, _P]),
     "pu_ctx_stream": (_P, [_P]),
     "pu_ctx_device_bytes": (_c_i64, [_P]),
     "pu_write_ceiling": (_c_int, [_c_int, _c_i64, _c_int, _P]),

@@ -267,4 +267,15 @@ int enqueue_ascbias(pu_ctx *c, double *lnl);
 // per device, guarded by ws_mutex(device)
 std::mutex &ws_mutex(int device);
 int ws_get(int device, size_t doubles, double **out, hipStream_t *st);
+// pu_distance.hip, for pu_bootstrap.hip: the model arguments of a pair call (host buffers), their
+// checks, and k_pair_newton queued on count matrices that are already on the device
+struct PairModel {
+    int K, C, n_codes;
+    const double *table, *evecs, *evals, *ivecs, *freqs, *rates, *cw;
+};
+int pair_check_model(const char *fn, const PairModel &m, double lo, double hi, double tol,
+                     int max_iter);
+int pair_newton_device(int device, hipStream_t st, const PairModel &m, double lo, double hi,
+                       double tol, int max_iter, const double *d_counts, int64_t n_batch,
+                       int64_t rows, double *d_out5, int64_t out_stride);
 }  // namespace pu

@@ -387,6 +387,43 @@ int check_model(const char *fn, const ModelIn &m, const Opt &o, int64_t n_pairs)
     return PU_OK;
 }
 
+// the model as k_pair_newton reads it: L [n][K], R [n][K], evals [K], rates [C], weights [C],
+// F(0) [n][n]; returns the mask of the codes whose tip vector is constant
+uint32_t pack_model(const ModelIn &m, int n, std::vector<double> &h) {
+    const int K = m.K, C = m.C;
+    uint32_t flat = 0;
+    h.assign((size_t)2 * n * K + K + 2 * C + (size_t)n * n, 0.0);
+    double *L = h.data(), *R = L + (size_t)n * K;
+    for (int u = 0; u < n; ++u) {
+        const double *x = m.table + (size_t)u * K;
+        bool same = true;
+        for (int i = 1; i < K; ++i) same = same && x[i] == x[0];
+        if (same) flat |= 1u << u;
+        for (int k = 0; k < K; ++k) {
+            double accl = 0.0, accr = 0.0;
+            for (int i = 0; i < K; ++i) {
+                accl += m.freqs[i] * x[i] * m.evecs[(size_t)i * K + k];
+                accr += m.ivecs[(size_t)k * K + i] * x[i];
+            }
+            L[(size_t)u * K + k] = accl;
+            R[(size_t)u * K + k] = accr;
+        }
+    }
+    std::copy(m.evals, m.evals + K, R + (size_t)n * K);
+    std::copy(m.rates, m.rates + C, R + (size_t)n * K + K);
+    std::copy(m.cw, m.cw + C, R + (size_t)n * K + K + C);
+    double Q = 0.0, *F0 = R + (size_t)n * K + K + 2 * C;
+    for (int c = 0; c < C; ++c) Q += m.cw[c];
+    for (int u = 0; u < n; ++u)
+        for (int v = 0; v < n; ++v) {
+            double acc = 0.0;
+            for (int i = 0; i < K; ++i)
+                acc += m.freqs[i] * m.table[(size_t)u * K + i] * m.table[(size_t)v * K + i];
+            F0[(size_t)u * n + v] = Q * acc;
+        }
+    return flat;
+}
+
 // sites per segment of k_pair_counts: a function of n_sites alone (at most 32 segments)
 int64_t seg_sites(int64_t S) {
     const int64_t per = ((S + 31) / 32 + kCH - 1) / kCH * kCH;
@@ -432,36 +469,7 @@ int run_pairs(int device, hipStream_t st, const Shape &s, const uint8_t *d_codes
                                    hipMemcpyHostToDevice, st));
     uint32_t flat = 0;
     if (m) {
-        const int K = m->K, C = m->C;
-        D.h_model.assign((size_t)2 * n * K + K + 2 * C + (size_t)n * n, 0.0);
-        double *L = D.h_model.data(), *R = L + (size_t)n * K;
-        for (int u = 0; u < n; ++u) {
-            const double *x = m->table + (size_t)u * K;
-            bool same = true;
-            for (int i = 1; i < K; ++i) same = same && x[i] == x[0];
-            if (same) flat |= 1u << u;
-            for (int k = 0; k < K; ++k) {
-                double accl = 0.0, accr = 0.0;
-                for (int i = 0; i < K; ++i) {
-                    accl += m->freqs[i] * x[i] * m->evecs[(size_t)i * K + k];
-                    accr += m->ivecs[(size_t)k * K + i] * x[i];
-                }
-                L[(size_t)u * K + k] = accl;
-                R[(size_t)u * K + k] = accr;
-            }
-        }
-        std::copy(m->evals, m->evals + K, R + (size_t)n * K);
-        std::copy(m->rates, m->rates + C, R + (size_t)n * K + K);
-        std::copy(m->cw, m->cw + C, R + (size_t)n * K + K + C);
-        double Q = 0.0, *F0 = R + (size_t)n * K + K + 2 * C;
-        for (int c = 0; c < C; ++c) Q += m->cw[c];
-        for (int u = 0; u < n; ++u)
-            for (int v = 0; v < n; ++v) {
-                double acc = 0.0;
-                for (int i = 0; i < K; ++i)
-                    acc += m->freqs[i] * m->table[(size_t)u * K + i] * m->table[(size_t)v * K + i];
-                F0[(size_t)u * n + v] = Q * acc;
-            }
+        flat = pack_model(*m, n, D.h_model);
         if ((rc = grow(&D.d_model, &D.model_cap, D.h_model.size()))) return rc;
         HIPCHK(nullptr, hipMemcpyAsync(D.d_model, D.h_model.data(), D.h_model.size() * 8,
                                        hipMemcpyHostToDevice, st));
@@ -556,6 +564,62 @@ int upload(hipStream_t st, const uint8_t *codes, size_t n_codes_bytes, const dou
 }
 
 }  // namespace
+
+// ---- for pu_bootstrap.hip: the Newton step on count matrices that are already on the device
+
+namespace pu {
+
+int pair_check_model(const char *fn, const PairModel &pm, double lo, double hi, double tol,
+                     int max_iter) {
+    if (pm.n_codes < 1 || pm.n_codes > kMaxCodes)
+        return set_err(nullptr, PU_E_ARG, "%s: n_codes = %d is outside [1, %d]", fn, pm.n_codes,
+                       kMaxCodes);
+    const ModelIn m{pm.K, pm.C, pm.table, pm.evecs, pm.evals, pm.ivecs, pm.freqs, pm.rates, pm.cw};
+    const Opt o{nullptr, lo, hi, tol, max_iter};
+    return check_model(fn, m, o, 0);
+}
+
+// k_pair_newton over d_counts [n_batch][rows][n_codes^2], queued on st; the row of (b, i) lands
+// at d_out5 + 5 (b out_stride + i).  The start is sqrt(lo hi), as in a pair call without t0.
+int pair_newton_device(int device, hipStream_t st, const PairModel &pm, double lo, double hi,
+                       double tol, int max_iter, const double *d_counts, int64_t n_batch,
+                       int64_t rows, double *d_out5, int64_t out_stride) {
+    DistState &D = g_dist[device];
+    std::lock_guard<std::mutex> lk(D.mu);
+    if (D.done) HIPCHK(nullptr, hipEventSynchronize(D.done));
+    else HIPCHK(nullptr, hipEventCreateWithFlags(&D.done, hipEventDisableTiming));
+    const ModelIn m{pm.K, pm.C, pm.table, pm.evecs, pm.evals, pm.ivecs, pm.freqs, pm.rates, pm.cw};
+    const int n = pm.n_codes;
+    NewtonPairArgs q;
+    q.flat = pack_model(m, n, D.h_model);
+    if (int rc = grow(&D.d_model, &D.model_cap, D.h_model.size())) return rc;
+    HIPCHK(nullptr, hipMemcpyAsync(D.d_model, D.h_model.data(), D.h_model.size() * 8,
+                                   hipMemcpyHostToDevice, st));
+    q.model = D.d_model;
+    q.t0 = nullptr;
+    q.n_codes = n;
+    q.C = m.C;
+    q.lo = lo;
+    q.hi = hi;
+    q.tol = tol;
+    q.max_iter = max_iter;
+    const bool one = out_stride == rows;  // the rows of all batches are one list
+    const int64_t n_launch = one ? 1 : n_batch, per = one ? n_batch * rows : rows;
+    for (int64_t b = 0; b < n_launch; ++b) {
+        q.counts = d_counts + (size_t)b * rows * n * n;
+        q.out5 = d_out5 + 5 * b * out_stride;
+        q.n_pairs = per;
+        const dim3 g2((unsigned)((per + kNW - 1) / kNW));
+        if (m.K == 2) hipLaunchKernelGGL(k_pair_newton<2>, g2, dim3(64 * kNW), 0, st, q);
+        else if (m.K == 4) hipLaunchKernelGGL(k_pair_newton<4>, g2, dim3(64 * kNW), 0, st, q);
+        else hipLaunchKernelGGL(k_pair_newton<20>, g2, dim3(64 * kNW), 0, st, q);
+        HIPCHK(nullptr, hipGetLastError());
+    }
+    HIPCHK(nullptr, hipEventRecord(D.done, st));
+    return PU_OK;
+}
+
+}  // namespace pu
 
 extern "C" {
 

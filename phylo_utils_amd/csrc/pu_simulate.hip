@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "pu_ctx.h"
+#include "pu_philox.h"
 
 // Built, tested and measured on gfx950 only (wave64, the launch shapes below).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -93,23 +94,9 @@ struct CumArgs {
     double *cum;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11); only x0 and x1 of the output are used
+// the draw at address (seed, g, d): Philox4x32-10 with counter word 3 = 0 (pu_philox.h)
 __device__ __forceinline__ double sim_u(uint64_t seed, uint64_t g, uint32_t d) {
-    uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = d, c3 = 0u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint64_t m = ((uint64_t)(c1 >> 5) << 26) | (uint64_t)(c0 >> 6);
-    return (double)m * 0x1p-53;
+    return philox_u(seed, g, d, 0u);
 }
 
 // pick over n cumulative sums in memory: the first j with cum_j > u * cum_{n-1}, else n - 1

@@ -29,7 +29,9 @@ matrix of the pairwise ML distances (``phylo_utils_amd.distance``, the reference
 ``-s aln.fasta -m MODEL --nj {nj,bionj} [-o tree.nwk]`` needs no ``-t`` either: the tree is the
 neighbour-joining (or BIONJ) tree of those distances (``phylo_utils_amd.nj``; the reference has
 no tree builder), written as Newick to ``-o`` when given, and the ``lnL = `` line is that tree's,
-after ``--optimise`` when asked.
+after ``--optimise`` when asked; with ``--bootstrap R`` (and the seed of ``--seed``) the Newick
+carries, as internal node labels, the support in percent of every split over R bootstrap
+replicates (``phylo_utils_amd.bootstrap``).
 """
 from __future__ import annotations
 
@@ -150,6 +152,9 @@ def parse_cli(argv=None):
     ap.add_argument("--nj", choices=["nj", "bionj"], default=None,
                     help="take the tree from neighbour joining (or BIONJ) on the pairwise ML "
                          "distances of -s (no -t); -o receives its Newick")
+    ap.add_argument("--bootstrap", type=int, default=None, metavar="R",
+                    help="with --nj: label the tree's splits with their support in percent "
+                         "over R bootstrap replicates (seed: --seed)")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj")
     return ap.parse_args(argv)
@@ -157,6 +162,11 @@ def parse_cli(argv=None):
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "bootstrap", None) is not None:
+        if getattr(args, "nj", None) is None:
+            raise ValueError("--bootstrap needs --nj")
+        if args.bootstrap < 1:
+            raise ValueError("--bootstrap needs at least one replicate")
     if getattr(args, "nj", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None \
                 or args.tree is not None:
@@ -206,7 +216,10 @@ def run(args, out=None):
     tm.set_rate_model(build_rate_model(desc))
     tm.set_substitution_model(build_model(desc))
     if nj is not None:  # --nj: the tree from the alignment's own distances
-        tree = tm.set_nj_tree(method=nj)
+        if getattr(args, "bootstrap", None) is not None:
+            tree, _, _ = tm.bootstrap_nj(args.bootstrap, seed=args.seed, method=nj)
+        else:
+            tree = tm.set_nj_tree(method=nj)
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")

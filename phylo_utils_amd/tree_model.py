@@ -606,12 +606,9 @@ class TreeModel(object):
         return (states,) + tuple(extra) if extra else states
 
     # ------------------------------------------------------------------ outputs
-    def pairwise_distances(self, **kw):
-        """ML distances and variances of all pairs of the model's own alignment under its
-        substitution and rate models (``distance.pairwise_distances``; the reference's
-        phylo_utils/likelihood.py:226-236 per pair): (names in alignment order, D, V).  Needs no
-        tree and does not touch the context."""
-        from . import distance
+    def _coded_alignment(self):
+        """(codes, table, names in alignment order) of the model's alignment, for the calls that
+        work on coded rows (pairwise distances, the bootstrap)."""
         if self.alignment is None:
             raise ValueError("No alignment has been set")
         names = sorted(self.names, key=self.names.get)
@@ -622,6 +619,15 @@ class TreeModel(object):
             if coded is None or len(coded[1]) > 32:
                 raise ValueError("pairwise distances need tips of at most 32 distinct vectors")
             codes, table = coded
+        return codes, table, names
+
+    def pairwise_distances(self, **kw):
+        """ML distances and variances of all pairs of the model's own alignment under its
+        substitution and rate models (``distance.pairwise_distances``; the reference's
+        phylo_utils/likelihood.py:226-236 per pair): (names in alignment order, D, V).  Needs no
+        tree and does not touch the context."""
+        from . import distance
+        codes, table, names = self._coded_alignment()
         kw.setdefault("device", self.device)
         kw.setdefault("weights", np.asarray(self.siteweights, dtype=np.float64))
         return distance.pairwise_distances((codes, table, names), self.substitution_model,
@@ -639,6 +645,22 @@ class TreeModel(object):
                                     device=self.device)
         self.set_tree(tree)
         return tree
+
+    def bootstrap_nj(self, n_replicates=100, seed=0, method="nj", **distance_kw):
+        """``set_nj_tree`` with bootstrap support (``bootstrap.bootstrap_nj`` on the model's own
+        alignment and models): the reference tree becomes the model's tree, as ``set_nj_tree``
+        sets it, with every internal node that carries one of its splits labelled with the
+        split's support in percent over `n_replicates` resampled alignments.  Returns (tree,
+        support [n-3] of clusters n + m in join order, n_ok: the replicates counted)."""
+        from . import bootstrap
+        codes, table, names = self._coded_alignment()
+        distance_kw.setdefault("device", self.device)
+        distance_kw.setdefault("weights", np.asarray(self.siteweights, dtype=np.float64))
+        tree, support, n_ok = bootstrap.bootstrap_nj(
+            (codes, table, names), self.substitution_model, getattr(self, "rate_model", None),
+            n_replicates=n_replicates, seed=seed, method=method, min_length=1e-8, **distance_kw)
+        self.set_tree(tree)
+        return tree, support, n_ok
 
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
