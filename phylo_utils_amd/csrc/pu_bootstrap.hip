@@ -42,7 +42,8 @@
 //                       T = 32, P = 1).  One segment: the bins are written as fp64
 //                       [n_rep][n_pairs][n_codes^2], the layout k_pair_newton reads.
 //   k_boot_merge        several segments: their uint32 slabs added as integers, then to fp64.
-//   k_boot_matrix       the t column of out5 [n_rep][n_pairs][5] as matrices [n_rep][n][ld].
+//   (pu_nj.hip)         k_pair_matrix_all: the t column of out5 [n_rep][n_pairs][5] as matrices
+//                       [n_rep][n][ld].
 //   k_boot_ok           one workgroup per replicate: ok[r] = every upper-triangle entry finite.
 //   k_boot_splits       one workgroup per tree, thread w owns word w of every cluster's bitset:
 //                       cluster n + m is the OR of its children's, in join order (a thread reads
@@ -70,6 +71,7 @@
 #include <vector>
 
 #include "pu_ctx.h"
+#include "pu_service.h"
 #include "pu_philox.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -80,9 +82,6 @@ using namespace pu;
 
 namespace {
 
-constexpr int kMaxCodes = 32;
-constexpr int kCH = 128;                            // sites per staged chunk
-constexpr int kRow = kCH + 4;                       // staged code row stride in bytes
 constexpr size_t kLdsCap = 160 * 1024;              // LDS one workgroup may have
 constexpr int kMaxWaves = 4;                        // k_boot_pair_counts: pairs per workgroup
 constexpr int kMinTile = 4;                         // replicates per tile, at least
@@ -174,9 +173,6 @@ struct BootCountArgs {
     uint32_t *slabs;       // [segments][n_rep][n_pairs][n_codes^2] or null
 };
 
-// words between the bins of neighbouring lanes: odd, so the lanes start on different banks
-__host__ __device__ inline int bin_stride(int n_codes) { return (n_codes * n_codes) | 1; }
-
 __host__ inline size_t count_lds(int n_codes, int P, int T) {
     return ((size_t)P * T * bin_stride(n_codes) + (size_t)kCH * (T + 1)) * 4 + (size_t)2 * P * kRow;
 }
@@ -246,23 +242,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- matrices -----------------------------------------------------------------------------
-
-// one thread per matrix entry of every replicate; pair (i, j), i < j, is row
-// i n - i (i + 1) / 2 + j - i - 1 of the replicate's out5 rows; the diagonal is zero
-__global__ void __launch_bounds__(256)
-    k_boot_matrix(int n_rep, int n, const double *__restrict__ out5, double *__restrict__ D,
-                  int64_t ld) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x, nn = (int64_t)n * n;
-    if (e >= nn * n_rep) return;
-    const int64_t r = e / nn, k = e - r * nn;
-    const int i = (int)(k / n), j = (int)(k - (int64_t)i * n);
-    double d = 0.0;
-    if (i != j) {
-        const int64_t lo = min(i, j), hi = max(i, j), np = (nn - n) / 2;
-        d = out5[5 * (r * np + lo * n - lo * (lo + 1) / 2 + hi - lo - 1)];
-    }
-    D[(r * n + i) * ld + j] = d;
-}
 
 __global__ void __launch_bounds__(256)
     k_boot_ok(int n, const double *__restrict__ D, int64_t ld, int32_t *__restrict__ ok) {
@@ -352,53 +331,16 @@ __global__ void __launch_bounds__(256)
 
 // ---- host side ---------------------------------------------------------------------------
 
-// per-device buffers (grown, never shrunk), guarded by mu; `done` marks the end of the last
-// call's queued work, which the next call waits for before it touches them
-struct BootState {
-    std::mutex mu;
-    uint32_t *d_prefix = nullptr;
-    size_t prefix_cap = 0;
-    int64_t *d_total = nullptr;
-    size_t total_cap = 0;
-    int32_t *d_pairs = nullptr;
-    size_t pairs_cap = 0;
-    double *d_counts = nullptr;
-    size_t counts_cap = 0;
-    uint32_t *d_slabs = nullptr;
-    size_t slabs_cap = 0;
-    uint64_t *d_bits = nullptr;
-    size_t bits_cap = 0;
-    std::vector<int32_t> h_pairs;
-    hipEvent_t done = nullptr;
-    bool profile = false;
-    std::vector<hipEvent_t> ev;  // profiling: 3 per chunk (start, after the counts, after Newton)
-    int n_ev = 0;
+// per-device buffers of the bootstrap calls (DevState: pu_service.h)
+struct BootState : DevState {
+    DevBuf<uint32_t> prefix, slabs;
+    DevBuf<int64_t> total;
+    PairList pairs;
+    DevBuf<double> counts;
+    DevBuf<uint64_t> bits;
+    ChunkProfile prof;
 };
 BootState g_boot[64];
-
-template <class T>
-int grow(T **p, size_t *cap, size_t n) {
-    if (*cap >= n) return PU_OK;
-    dfree(*p);
-    *cap = 0;
-    if (int rc = dalloc(nullptr, p, n)) return rc;
-    *cap = n;
-    return PU_OK;
-}
-
-int begin(BootState &B) {
-    if (B.done) HIPCHK(nullptr, hipEventSynchronize(B.done));
-    else HIPCHK(nullptr, hipEventCreateWithFlags(&B.done, hipEventDisableTiming));
-    return PU_OK;
-}
-
-// marks the end of a call's queued work on every way out of it, an error return included: what
-// was queued before the error still reads the state's buffers
-struct Done {
-    BootState &B;
-    hipStream_t st;
-    ~Done() { (void)hipEventRecord(B.done, st); }
-};
 
 // N of host weights (NULL: n_sites), or an error: a weight that is negative, non-integer or
 // non-finite, or N outside [1, 2^31 - 1]
@@ -435,9 +377,9 @@ int check_reps(const char *fn, int64_t first_rep, int n_rep, int64_t n_sites) {
 int run_weights(int device, hipStream_t st, uint64_t seed, int64_t first_rep, int n_rep,
                 int64_t S, const double *d_w, int64_t N_host, uint32_t *d_W, int64_t ldw) {
     BootState &B = g_boot[device];
-    std::lock_guard<std::mutex> lk(B.mu);
-    if (int rc = begin(B)) return rc;
-    const Done done{B, st};
+    StateScope scope(B, st);
+    int rc;
+    if ((rc = scope.rc)) return rc;
     HIPCHK(nullptr, hipMemset2DAsync(d_W, (size_t)ldw * 4, 0, (size_t)S * 4, (size_t)n_rep, st));
     WeightArgs a;
     a.seed = seed;
@@ -449,58 +391,18 @@ int run_weights(int device, hipStream_t st, uint64_t seed, int64_t first_rep, in
     a.W = d_W;
     a.ldw = ldw;
     if (d_w) {
-        int rc;
-        if ((rc = grow(&B.d_prefix, &B.prefix_cap, (size_t)S))) return rc;
-        if ((rc = grow(&B.d_total, &B.total_cap, 1))) return rc;
-        hipLaunchKernelGGL(k_boot_prefix, dim3(1), dim3(kPT), 0, st, d_w, S, B.d_prefix, B.d_total);
+        if ((rc = B.prefix.reserve((size_t)S))) return rc;
+        if ((rc = B.total.reserve(1))) return rc;
+        hipLaunchKernelGGL(k_boot_prefix, dim3(1), dim3(kPT), 0, st, d_w, S, B.prefix.p, B.total.p);
         HIPCHK(nullptr, hipGetLastError());
-        a.prefix = B.d_prefix;
-        a.total = B.d_total;
+        a.prefix = B.prefix.p;
+        a.total = B.total.p;
     }
     const int64_t cols = N_host > 0 ? N_host : S;
     const dim3 grid((unsigned)std::min<int64_t>(1024, (cols + 255) / 256),
                     (unsigned)std::min(n_rep, 64));
     hipLaunchKernelGGL(k_boot_weights, grid, dim3(256), 0, st, a);
     HIPCHK(nullptr, hipGetLastError());
-    return PU_OK;
-}
-
-struct Shape {
-    int n_taxa, n_codes;
-    int64_t n_sites, n_pairs;
-    const int32_t *pairs;
-    int n_rep;
-};
-
-int check_shape(const char *fn, const Shape &s, const void *codes, const void *W) {
-    if (!codes || !W) return set_err(nullptr, PU_E_ARG, "%s: null buffer", fn);
-    if (s.n_rep < 1) return set_err(nullptr, PU_E_ARG, "%s: n_rep = %d", fn, s.n_rep);
-    if (s.n_taxa < 2 || s.n_sites <= 0)
-        return set_err(nullptr, PU_E_ARG, "%s: n_taxa = %d, n_sites = %lld", fn, s.n_taxa,
-                       (long long)s.n_sites);
-    if (s.n_codes < 1 || s.n_codes > kMaxCodes)
-        return set_err(nullptr, PU_E_ARG, "%s: n_codes = %d is outside [1, %d]", fn, s.n_codes,
-                       kMaxCodes);
-    const int64_t all = (int64_t)s.n_taxa * (s.n_taxa - 1) / 2;
-    if (s.n_pairs < 1 || (!s.pairs && s.n_pairs != all))
-        return set_err(nullptr, PU_E_ARG, "%s: n_pairs = %lld (without a pair list: all %lld)", fn,
-                       (long long)s.n_pairs, (long long)all);
-    if (s.pairs)
-        for (int64_t p = 0; p < s.n_pairs; ++p) {
-            const int i = s.pairs[2 * p], j = s.pairs[2 * p + 1];
-            if (i < 0 || j < 0 || i >= s.n_taxa || j >= s.n_taxa || i == j)
-                return set_err(nullptr, PU_E_ARG, "%s: pair %lld = (%d, %d) of %d taxa", fn,
-                               (long long)p, i, j, s.n_taxa);
-        }
-    return PU_OK;
-}
-
-int check_codes(const char *fn, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes) {
-    for (int64_t i = 0; i < (int64_t)n_taxa * n_sites; ++i)
-        if (codes[i] >= n_codes)
-            return set_err(nullptr, PU_E_ARG, "%s: taxon %lld site %lld: code %d >= n_codes = %d",
-                           fn, (long long)(i / n_sites), (long long)(i % n_sites), (int)codes[i],
-                           n_codes);
     return PU_OK;
 }
 
@@ -527,24 +429,11 @@ int run_counts(int device, hipStream_t st, const Shape &s, const uint8_t *d_code
                const uint32_t *d_W, int64_t ldw, const PairModel *pm, const Opt *o, double *d_out5,
                double *counts_host) {
     BootState &B = g_boot[device];
-    std::lock_guard<std::mutex> lk(B.mu);
+    StateScope scope(B, st);
     int rc;
-    if ((rc = begin(B))) return rc;
-    const Done done{B, st};
+    if ((rc = scope.rc)) return rc;
     const int n = s.n_codes, nb = n * n;
-    B.h_pairs.resize(2 * (size_t)s.n_pairs);
-    if (s.pairs) std::copy(s.pairs, s.pairs + 2 * s.n_pairs, B.h_pairs.begin());
-    else {
-        size_t k = 0;
-        for (int i = 0; i < s.n_taxa; ++i)
-            for (int j = i + 1; j < s.n_taxa; ++j) {
-                B.h_pairs[k++] = i;
-                B.h_pairs[k++] = j;
-            }
-    }
-    if ((rc = grow(&B.d_pairs, &B.pairs_cap, B.h_pairs.size()))) return rc;
-    HIPCHK(nullptr, hipMemcpyAsync(B.d_pairs, B.h_pairs.data(), B.h_pairs.size() * 4,
-                                   hipMemcpyHostToDevice, st));
+    if ((rc = B.pairs.upload(st, s.n_taxa, s.n_pairs, s.pairs))) return rc;
     // the tile: as many replicates as the call has, up to 64, while one pair's bins fit
     int T = 64;
     while (T > kMinTile && (count_lds(n, 1, T) > kLdsCap || T / 2 >= s.n_rep)) T >>= 1;
@@ -564,37 +453,21 @@ int run_counts(int device, hipStream_t st, const Shape &s, const uint8_t *d_code
     // PU_BOOT_REP_CHUNK the replicates; no result depends on either)
     const size_t per = (size_t)nb * (8 + (n_seg > 1 ? 4 * (size_t)n_seg : 0));
     const int64_t room = std::max<int64_t>(1, (int64_t)(kBootWsBytes / per));
-    int64_t pc = s.n_pairs, rc_n;
-    if (const char *env = getenv("PU_DIST_CHUNK")) {
-        const long long v = atoll(env);
-        if (v > 0) pc = std::min<int64_t>(pc, v);
-    }
+    int64_t pc = env_cap("PU_DIST_CHUNK", s.n_pairs), rc_n;
     if (room >= (int64_t)T * pc) rc_n = std::min<int64_t>(s.n_rep, room / pc / T * T);
     else {
         rc_n = std::min<int64_t>(s.n_rep, T);
         pc = std::max<int64_t>(1, std::min(pc, room / rc_n));
     }
-    if (const char *env = getenv("PU_BOOT_REP_CHUNK")) {
-        const long long v = atoll(env);
-        if (v > 0) rc_n = std::min<int64_t>(rc_n, v);
-    }
-    if ((rc = grow(&B.d_counts, &B.counts_cap, (size_t)rc_n * pc * nb))) return rc;
-    if (n_seg > 1 && (rc = grow(&B.d_slabs, &B.slabs_cap, (size_t)n_seg * rc_n * pc * nb)))
-        return rc;
-    B.n_ev = 0;
-    if (B.profile) {
-        const int64_t n_chunks = (s.n_rep + rc_n - 1) / rc_n * ((s.n_pairs + pc - 1) / pc);
-        while ((int64_t)B.ev.size() < 3 * n_chunks) {
-            hipEvent_t e;
-            HIPCHK(nullptr, hipEventCreate(&e));
-            B.ev.push_back(e);
-        }
-    }
+    rc_n = env_cap("PU_BOOT_REP_CHUNK", rc_n);
+    if ((rc = B.counts.reserve((size_t)rc_n * pc * nb))) return rc;
+    if (n_seg > 1 && (rc = B.slabs.reserve((size_t)n_seg * rc_n * pc * nb))) return rc;
+    if ((rc = B.prof.reserve((s.n_rep + rc_n - 1) / rc_n * ((s.n_pairs + pc - 1) / pc)))) return rc;
     for (int64_t r0 = 0; r0 < s.n_rep; r0 += rc_n) {
         const int64_t nr = std::min<int64_t>(rc_n, s.n_rep - r0);
         for (int64_t p0 = 0; p0 < s.n_pairs; p0 += pc) {
             const int64_t np = std::min(pc, s.n_pairs - p0);
-            if (B.profile) HIPCHK(nullptr, hipEventRecord(B.ev[B.n_ev], st));
+            if ((rc = B.prof.mark(0, st))) return rc;
             BootCountArgs a;
             a.codes = d_codes;
             a.ld = ld;
@@ -602,14 +475,14 @@ int run_counts(int device, hipStream_t st, const Shape &s, const uint8_t *d_code
             a.W = d_W + r0 * ldw;
             a.ldw = ldw;
             a.n_rep = (int)nr;
-            a.pairs = B.d_pairs + 2 * p0;
+            a.pairs = B.pairs.d.p + 2 * p0;
             a.n_pairs = np;
             a.n_codes = n;
             a.P = P;
             a.T = T;
             a.seg = seg;
-            a.out = B.d_counts;
-            a.slabs = n_seg > 1 ? B.d_slabs : nullptr;
+            a.out = B.counts.p;
+            a.slabs = n_seg > 1 ? B.slabs.p : nullptr;
             const dim3 grid((unsigned)((np + P - 1) / P), (unsigned)((nr + T - 1) / T),
                             (unsigned)n_seg);
             if (grid.y > 65535u)
@@ -620,39 +493,28 @@ int run_counts(int device, hipStream_t st, const Shape &s, const uint8_t *d_code
             const size_t ne = (size_t)nr * np * nb;
             if (n_seg > 1) {
                 hipLaunchKernelGGL(k_boot_merge, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
-                                   st, B.d_slabs, (int)n_seg, ne, B.d_counts);
+                                   st, B.slabs.p, (int)n_seg, ne, B.counts.p);
                 HIPCHK(nullptr, hipGetLastError());
             }
-            if (B.profile) HIPCHK(nullptr, hipEventRecord(B.ev[B.n_ev + 1], st));
+            if ((rc = B.prof.mark(1, st))) return rc;
             if (pm) {
                 if ((rc = pair_newton_device(device, st, *pm, o->lo, o->hi, o->tol, o->max_iter,
-                                             B.d_counts, nr, np,
+                                             B.counts.p, nr, np,
                                              d_out5 + 5 * (r0 * s.n_pairs + p0), s.n_pairs)))
                     return rc;
             } else if (np == s.n_pairs) {
-                HIPCHK(nullptr, hipMemcpyAsync(counts_host + (size_t)r0 * s.n_pairs * nb, B.d_counts,
+                HIPCHK(nullptr, hipMemcpyAsync(counts_host + (size_t)r0 * s.n_pairs * nb, B.counts.p,
                                                ne * 8, hipMemcpyDeviceToHost, st));
             } else {
                 for (int64_t r = 0; r < nr; ++r)
                     HIPCHK(nullptr, hipMemcpyAsync(
                                         counts_host + ((size_t)(r0 + r) * s.n_pairs + p0) * nb,
-                                        B.d_counts + (size_t)r * np * nb, (size_t)np * nb * 8,
+                                        B.counts.p + (size_t)r * np * nb, (size_t)np * nb * 8,
                                         hipMemcpyDeviceToHost, st));
             }
-            if (B.profile) {
-                HIPCHK(nullptr, hipEventRecord(B.ev[B.n_ev + 2], st));
-                B.n_ev += 3;
-            }
+            if ((rc = B.prof.mark(2, st))) return rc;
         }
     }
-    return PU_OK;
-}
-
-int run_matrix(hipStream_t st, int n_rep, int n, const double *d_out5, double *d_D, int64_t ld) {
-    const int64_t ne = (int64_t)n_rep * n * n;
-    hipLaunchKernelGGL(k_boot_matrix, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, n_rep,
-                       n, d_out5, d_D, ld);
-    HIPCHK(nullptr, hipGetLastError());
     return PU_OK;
 }
 
@@ -683,13 +545,12 @@ int check_joins(const char *fn, const char *what, int64_t tree, int n, const int
 int run_support(int device, hipStream_t st, int n, int n_rep, const int32_t *d_ref_joins,
                 const int32_t *d_joins, const int32_t *d_ok, double *d_support, int32_t *d_n_ok) {
     BootState &B = g_boot[device];
-    std::lock_guard<std::mutex> lk(B.mu);
+    StateScope scope(B, st);
     int rc;
-    if ((rc = begin(B))) return rc;
-    const Done done{B, st};
+    if ((rc = scope.rc)) return rc;
     const int ns = n - 3, nw = (n + 63) / 64;
-    if ((rc = grow(&B.d_bits, &B.bits_cap, (size_t)(1 + n_rep) * std::max(ns, 1) * nw))) return rc;
-    uint64_t *ref = B.d_bits, *bits = ref + (size_t)std::max(ns, 1) * nw;
+    if ((rc = B.bits.reserve((size_t)(1 + n_rep) * std::max(ns, 1) * nw))) return rc;
+    uint64_t *ref = B.bits.p, *bits = ref + (size_t)std::max(ns, 1) * nw;
     if (ns > 0) {
         hipLaunchKernelGGL(k_boot_splits, dim3(1), dim3(64), (size_t)ns, st, d_ref_joins, n, nw,
                            ref);
@@ -701,31 +562,6 @@ int run_support(int device, hipStream_t st, int n, int n_rep, const int32_t *d_r
                        n_rep, ref, bits, d_ok, d_support, d_n_ok);
     HIPCHK(nullptr, hipGetLastError());
     return PU_OK;
-}
-
-int host_stream(int device, hipStream_t *st) {
-    double *unused;
-    return ws_get(device, 1, &unused, st);
-}
-
-template <class T>
-int to_device(hipStream_t st, const T *src, size_t n, T **dst) {
-    if (int rc = dalloc(nullptr, dst, n)) return rc;
-    HIPCHK(nullptr, hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return PU_OK;
-}
-
-template <class T>
-int to_host(hipStream_t st, T *dst, const T *src, size_t n) {
-    if (n) HIPCHK(nullptr, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    return PU_OK;
-}
-
-int finish(const char *fn, hipStream_t st, int rc) {
-    // the queued work reads the buffers the caller is about to free: wait for it either way
-    const hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) rc = set_err(nullptr, PU_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return rc;
 }
 
 }  // namespace
@@ -761,20 +597,14 @@ int pu_boot_weights(int device, uint64_t seed, int64_t first_rep, int n_rep, int
     if ((rc = host_total(fn, site_weights, n_sites, &N))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    hipStream_t st;
-    if ((rc = host_stream(device, &st))) return rc;
-    double *d_sw = nullptr;
-    uint32_t *d_W = nullptr;
+    HostCall h(device);
     const size_t nW = (size_t)n_rep * n_sites;
-    if (site_weights) rc = to_device(st, site_weights, (size_t)n_sites, &d_sw);
-    if (!rc) rc = dalloc(nullptr, &d_W, nW);
-    if (!rc) rc = run_weights(device, st, seed, first_rep, n_rep, n_sites, d_sw, N, d_W, n_sites);
-    if (!rc) rc = to_host(st, w_out, d_W, nW);
-    rc = finish(fn, st, rc);
-    dfree(d_sw);
-    dfree(d_W);
-    return rc;
+    const double *d_sw = h.to_device(site_weights, (size_t)n_sites);
+    uint32_t *d_W = h.alloc<uint32_t>(nW);
+    if (!h.rc)
+        h.rc = run_weights(device, h.st, seed, first_rep, n_rep, n_sites, d_sw, N, d_W, n_sites);
+    h.to_host(w_out, d_W, nW);
+    return h.finish(fn);
 }
 
 int pu_boot_pair_counts(int device, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes,
@@ -783,25 +613,19 @@ int pu_boot_pair_counts(int device, const uint8_t *codes, int n_taxa, int64_t n_
     const char *fn = "pu_boot_pair_counts";
     const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs, n_rep};
     int rc;
-    if ((rc = check_shape(fn, s, codes, W))) return rc;
+    if ((rc = check_shape(fn, s, !codes || !W))) return rc;
     if (!counts_out) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
     if ((rc = check_codes(fn, codes, n_taxa, n_sites, n_codes))) return rc;
     if ((rc = check_W(fn, W, n_rep, n_sites))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    hipStream_t st;
-    if ((rc = host_stream(device, &st))) return rc;
-    uint8_t *d_codes = nullptr;
-    uint32_t *d_W = nullptr;
-    rc = to_device(st, codes, (size_t)n_taxa * n_sites, &d_codes);
-    if (!rc) rc = to_device(st, W, (size_t)n_rep * n_sites, &d_W);
-    if (!rc) rc = run_counts(device, st, s, d_codes, n_sites, d_W, n_sites, nullptr, nullptr,
-                             nullptr, counts_out);
-    rc = finish(fn, st, rc);
-    dfree(d_codes);
-    dfree(d_W);
-    return rc;
+    HostCall h(device);
+    const uint8_t *d_codes = h.to_device(codes, (size_t)n_taxa * n_sites);
+    const uint32_t *d_W = h.to_device(W, (size_t)n_rep * n_sites);
+    if (!h.rc)
+        h.rc = run_counts(device, h.st, s, d_codes, n_sites, d_W, n_sites, nullptr, nullptr,
+                          nullptr, counts_out);
+    return h.finish(fn);
 }
 
 int pu_boot_distances_device(int device, void *stream, int n_states, int n_cat, int n_codes,
@@ -817,7 +641,7 @@ int pu_boot_distances_device(int device, void *stream, int n_states, int n_cat, 
                        cat_weights};
     const Opt o{lo, hi, tol, max_iter};
     int rc;
-    if ((rc = check_shape(fn, s, d_codes, d_W))) return rc;
+    if ((rc = check_shape(fn, s, !d_codes || !d_W))) return rc;
     if (!d_out5) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
     if (ld < n_sites || ldw < n_sites)
         return set_err(nullptr, PU_E_ARG, "%s: row strides %lld, %lld below n_sites = %lld", fn,
@@ -831,7 +655,7 @@ int pu_boot_distances_device(int device, void *stream, int n_states, int n_cat, 
     DeviceGuard g(device);
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_counts(device, st, s, d_codes, ld, d_W, ldw, &pm, &o, d_out5, nullptr))) return rc;
-    if (d_D) return run_matrix(st, n_rep, n_taxa, d_out5, d_D, ldd);
+    if (d_D) return pair_matrix_all(st, n_rep, n_taxa, d_out5, d_D, ldd);
     return PU_OK;
 }
 
@@ -847,30 +671,22 @@ int pu_boot_distances(int device, int n_states, int n_cat, int n_codes, const do
                        cat_weights};
     const Opt o{lo, hi, tol, max_iter};
     int rc;
-    if ((rc = check_shape(fn, s, codes, W))) return rc;
+    if ((rc = check_shape(fn, s, !codes || !W))) return rc;
     if (!out5_out) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
     if ((rc = pair_check_model(fn, pm, lo, hi, tol, max_iter))) return rc;
     if ((rc = check_codes(fn, codes, n_taxa, n_sites, n_codes))) return rc;
     if ((rc = check_W(fn, W, n_rep, n_sites))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    hipStream_t st;
-    if ((rc = host_stream(device, &st))) return rc;
-    uint8_t *d_codes = nullptr;
-    uint32_t *d_W = nullptr;
-    double *d_out = nullptr;
+    HostCall h(device);
     const size_t n_out = 5 * (size_t)n_rep * n_pairs;
-    rc = to_device(st, codes, (size_t)n_taxa * n_sites, &d_codes);
-    if (!rc) rc = to_device(st, W, (size_t)n_rep * n_sites, &d_W);
-    if (!rc) rc = dalloc(nullptr, &d_out, n_out);
-    if (!rc) rc = run_counts(device, st, s, d_codes, n_sites, d_W, n_sites, &pm, &o, d_out, nullptr);
-    if (!rc) rc = to_host(st, out5_out, d_out, n_out);
-    rc = finish(fn, st, rc);
-    dfree(d_codes);
-    dfree(d_W);
-    dfree(d_out);
-    return rc;
+    const uint8_t *d_codes = h.to_device(codes, (size_t)n_taxa * n_sites);
+    const uint32_t *d_W = h.to_device(W, (size_t)n_rep * n_sites);
+    double *d_out = h.alloc<double>(n_out);
+    if (!h.rc)
+        h.rc = run_counts(device, h.st, s, d_codes, n_sites, d_W, n_sites, &pm, &o, d_out, nullptr);
+    h.to_host(out5_out, d_out, n_out);
+    return h.finish(fn);
 }
 
 int pu_split_support_device(int device, void *stream, int n, int n_rep, const int32_t *d_ref_joins,
@@ -901,27 +717,16 @@ int pu_split_support(int device, int n, int n_rep, const int32_t *ref_joins,
         if ((rc = check_joins(fn, "replicate", r, n, joins + r * (n - 2) * 2))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    hipStream_t st;
-    if ((rc = host_stream(device, &st))) return rc;
+    HostCall h(device);
     const size_t nj = (size_t)(n - 2) * 2;
-    int32_t *d_ref = nullptr, *d_jo = nullptr, *d_ok = nullptr, *d_nok = nullptr;
-    double *d_sup = nullptr;
-    rc = to_device(st, ref_joins, nj, &d_ref);
-    if (!rc) rc = to_device(st, joins, nj * n_rep, &d_jo);
-    if (!rc && ok) rc = to_device(st, ok, (size_t)n_rep, &d_ok);
-    if (!rc) rc = dalloc(nullptr, &d_sup, (size_t)std::max(n - 3, 1));
-    if (!rc) rc = dalloc(nullptr, &d_nok, 1);
-    if (!rc) rc = run_support(device, st, n, n_rep, d_ref, d_jo, d_ok, d_sup, d_nok);
-    if (!rc) rc = to_host(st, support_out, d_sup, (size_t)(n - 3));
-    if (!rc) rc = to_host(st, n_ok_out, d_nok, 1);
-    rc = finish(fn, st, rc);
-    dfree(d_ref);
-    dfree(d_jo);
-    dfree(d_ok);
-    dfree(d_sup);
-    dfree(d_nok);
-    return rc;
+    const int32_t *d_ref = h.to_device(ref_joins, nj), *d_jo = h.to_device(joins, nj * n_rep);
+    const int32_t *d_ok = h.to_device(ok, (size_t)n_rep);
+    double *d_sup = h.alloc<double>((size_t)std::max(n - 3, 1));
+    int32_t *d_nok = h.alloc<int32_t>(1);
+    if (!h.rc) h.rc = run_support(device, h.st, n, n_rep, d_ref, d_jo, d_ok, d_sup, d_nok);
+    h.to_host(support_out, d_sup, (size_t)(n - 3));
+    h.to_host(n_ok_out, d_nok, 1);
+    return h.finish(fn);
 }
 
 int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes,
@@ -952,22 +757,18 @@ int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes
     if ((rc = check_codes(fn, codes, n, n_sites, n_codes))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    hipStream_t st;
-    if ((rc = host_stream(device, &st))) return rc;
+    HostCall h(device);
+    hipStream_t st = h.st;
     const int64_t np = (int64_t)n * (n - 1) / 2;
     const size_t nj = (size_t)(n - 2) * 2, nn = (size_t)n * n, R = (size_t)n_rep;
-    uint8_t *d_codes = nullptr;
-    uint32_t *d_W = nullptr;
-    double *d_sw = nullptr, *d_f = nullptr;  // d_f: every fp64 buffer of the call
-    int32_t *d_i = nullptr;                  // every int32 buffer
-    rc = to_device(st, codes, (size_t)n * n_sites, &d_codes);
-    if (!rc && site_weights) rc = to_device(st, site_weights, (size_t)n_sites, &d_sw);
-    if (!rc) rc = dalloc(nullptr, &d_W, R * n_sites);
+    const uint8_t *d_codes = h.to_device(codes, (size_t)n * n_sites);
+    const double *d_sw = h.to_device(site_weights, (size_t)n_sites);
+    uint32_t *d_W = h.alloc<uint32_t>(R * n_sites);
     const size_t n_f = (1 + R) * (5 * (size_t)np + nn + nj + 1) + (size_t)n;
-    if (!rc) rc = dalloc(nullptr, &d_f, n_f);
-    if (!rc) rc = dalloc(nullptr, &d_i, (1 + R) * (nj + 2) + R + 1);
-    if (!rc) {
+    double *d_f = h.alloc<double>(n_f);                            // every fp64 buffer of the call
+    int32_t *d_i = h.alloc<int32_t>((1 + R) * (nj + 2) + R + 1);  // every int32 buffer
+    if (!h.rc) {
+        int &rc = h.rc;  // the chain below stops at the call's first error
         double *o5_ref = d_f, *o5 = o5_ref + 5 * np, *D_ref = o5 + 5 * np * R, *D = D_ref + nn;
         double *len_ref = D + nn * R, *len = len_ref + nj, *rl_ref = len + nj * R, *rl = rl_ref + 1;
         double *sup = rl + R;
@@ -995,52 +796,22 @@ int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes
         }
         if (!rc) rc = pu_nj_device(device, st, method, n_rep, n, D, n, jo, len, ro, rl, nullptr);
         if (!rc) rc = run_support(device, st, n, n_rep, jo_ref, jo, ok, sup, nok);
-        if (!rc) rc = to_host(st, ref_joins_out, jo_ref, nj);
-        if (!rc) rc = to_host(st, ref_lens_out, len_ref, nj);
-        if (!rc) rc = to_host(st, ref_root_out, ro_ref, 2);
-        if (!rc) rc = to_host(st, ref_root_len_out, rl_ref, 1);
-        if (!rc) rc = to_host(st, support_out, sup, (size_t)(n - 3));
-        if (!rc) rc = to_host(st, n_ok_out, nok, 1);
-        if (!rc && rep_joins_out) rc = to_host(st, rep_joins_out, jo, nj * R);
-        if (!rc && rep_roots_out) rc = to_host(st, rep_roots_out, ro, 2 * R);
+        h.to_host(ref_joins_out, jo_ref, nj);
+        h.to_host(ref_lens_out, len_ref, nj);
+        h.to_host(ref_root_out, ro_ref, 2);
+        h.to_host(ref_root_len_out, rl_ref, 1);
+        h.to_host(support_out, sup, (size_t)(n - 3));
+        h.to_host(n_ok_out, nok, 1);
+        if (rep_joins_out) h.to_host(rep_joins_out, jo, nj * R);
+        if (rep_roots_out) h.to_host(rep_roots_out, ro, 2 * R);
     }
-    rc = finish(fn, st, rc);
-    dfree(d_codes);
-    dfree(d_W);
-    dfree(d_sw);
-    dfree(d_f);
-    dfree(d_i);
-    return rc;
+    return h.finish(fn);
 }
 
-int pu_boot_profile(int device, int on) {
-    if (device < 0 || device >= 64) return set_err(nullptr, PU_E_ARG, "device %d", device);
-    BootState &B = g_boot[device];
-    std::lock_guard<std::mutex> lk(B.mu);
-    B.profile = on != 0;
-    B.n_ev = 0;
-    return PU_OK;
-}
+int pu_boot_profile(int device, int on) { return profile_set(g_boot, device, on); }
 
 int pu_boot_kernel_ms(int device, double *counts_ms, double *newton_ms) {
-    if (device < 0 || device >= 64 || !counts_ms || !newton_ms)
-        return set_err(nullptr, PU_E_ARG, "pu_boot_kernel_ms: bad argument");
-    BootState &B = g_boot[device];
-    std::lock_guard<std::mutex> lk(B.mu);
-    if (!B.n_ev) return set_err(nullptr, PU_E_STATE, "pu_boot_kernel_ms: nothing recorded");
-    DeviceGuard g(device);
-    HIPCHK(nullptr, hipEventSynchronize(B.ev[B.n_ev - 1]));
-    double c = 0.0, w = 0.0;
-    for (int i = 0; i < B.n_ev; i += 3) {
-        float a = 0.f, b = 0.f;
-        HIPCHK(nullptr, hipEventElapsedTime(&a, B.ev[i], B.ev[i + 1]));
-        HIPCHK(nullptr, hipEventElapsedTime(&b, B.ev[i + 1], B.ev[i + 2]));
-        c += a;
-        w += b;
-    }
-    *counts_ms = c;
-    *newton_ms = w;
-    return PU_OK;
+    return profile_ms("pu_boot_kernel_ms", g_boot, device, counts_ms, newton_ms);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // pu_ctx.h -- the device context behind the C ABI and the helpers every C-ABI translation
 // unit shares (pu_capi.cpp: contexts, planner, traversal; pu_edge.cpp: edge likelihoods,
-// derivatives and branch-length optimisation).  Not part of the public ABI.
+// derivatives and branch-length optimisation).  The host layer of the stateless calls (device
+// buffers, per-device state, host-call scope, pair-call argument rules) is pu_service.h.  Not
+// part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

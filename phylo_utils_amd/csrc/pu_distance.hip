@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "pu_ctx.h"
+#include "pu_service.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "pu_distance.hip: gfx950 only, as the other kernel files of this library"
@@ -54,10 +55,7 @@ using namespace pu;
 
 namespace {
 
-constexpr int kMaxCodes = 32;                       // 8 KB of bins per pair
 constexpr int kMaxCat = PU_PAIR_MAX_CAT;            // rates and weights in LDS
-constexpr int kCH = 128;                            // sites per staged chunk
-constexpr int kRow = kCH + 4;                       // staged row stride in bytes (33 words: odd)
 constexpr size_t kCountLds = 40 * 1024;             // LDS of one k_pair_counts workgroup
 constexpr size_t kDistWsBytes = (size_t)256 << 20;  // count matrices (and slabs) of one chunk
 constexpr int kNW = 4;                              // k_pair_newton: pairs (waves) per workgroup
@@ -73,9 +71,6 @@ struct CountArgs {
     int64_t seg;           // sites per segment (a multiple of kCH); blockIdx.y: the segment
     double *out;           // [segments][n_pairs][n_codes^2]
 };
-
-// doubles between the bins of neighbouring lanes: odd, so the lanes start on different banks
-__host__ __device__ inline int bin_stride(int n_codes) { return (n_codes * n_codes) | 1; }
 
 __host__ inline size_t count_lds(int n_codes, int P) {
     return ((size_t)P * bin_stride(n_codes) + kCH) * 8 + (size_t)2 * P * kRow;
@@ -288,75 +283,14 @@ __global__ void __launch_bounds__(64 * kNW) k_pair_newton(NewtonPairArgs a) {
 
 // ---- host side ---------------------------------------------------------------------------
 
-// per-device buffers of the pair calls (grown, never shrunk), guarded by mu; `done` marks the end
-// of the last call's queued work, which the next call waits for before it touches them
-struct DistState {
-    std::mutex mu;
-    int32_t *d_pairs = nullptr;
-    size_t pairs_cap = 0;
-    double *d_t0 = nullptr;
-    size_t t0_cap = 0;
-    double *d_model = nullptr;
-    size_t model_cap = 0;
-    double *d_counts = nullptr;
-    size_t counts_cap = 0;
-    double *d_slabs = nullptr;
-    size_t slabs_cap = 0;
-    hipEvent_t done = nullptr;
-    std::vector<int32_t> h_pairs;
+// per-device buffers of the pair calls and their host staging copies (DevState: pu_service.h)
+struct DistState : DevState {
+    PairList pairs;
+    DevBuf<double> t0, model, counts, slabs;
     std::vector<double> h_t0, h_model;
-    bool profile = false;
-    std::vector<hipEvent_t> ev;  // profiling: 3 per chunk (start, after the counts, after Newton)
-    int n_ev = 0;
+    ChunkProfile prof;
 };
 DistState g_dist[64];
-
-template <class T>
-int grow(T **p, size_t *cap, size_t n) {
-    if (*cap >= n) return PU_OK;
-    dfree(*p);
-    *cap = 0;
-    if (int rc = dalloc(nullptr, p, n)) return rc;
-    *cap = n;
-    return PU_OK;
-}
-
-struct Shape {
-    int n_taxa, n_codes;
-    int64_t n_sites, n_pairs;
-    const int32_t *pairs;
-};
-
-int check_shape(const char *fn, const Shape &s, const void *codes) {
-    if (!codes) return set_err(nullptr, PU_E_ARG, "%s: null codes", fn);
-    if (s.n_taxa < 2 || s.n_sites <= 0)
-        return set_err(nullptr, PU_E_ARG, "%s: n_taxa = %d, n_sites = %lld", fn, s.n_taxa,
-                       (long long)s.n_sites);
-    if (s.n_codes < 1 || s.n_codes > kMaxCodes)
-        return set_err(nullptr, PU_E_ARG, "%s: n_codes = %d is outside [1, %d]", fn, s.n_codes,
-                       kMaxCodes);
-    const int64_t all = (int64_t)s.n_taxa * (s.n_taxa - 1) / 2;
-    if (s.n_pairs < 1 || (!s.pairs && s.n_pairs != all))
-        return set_err(nullptr, PU_E_ARG, "%s: n_pairs = %lld (without a pair list: all %lld)", fn,
-                       (long long)s.n_pairs, (long long)all);
-    if (s.pairs)
-        for (int64_t p = 0; p < s.n_pairs; ++p) {
-            const int i = s.pairs[2 * p], j = s.pairs[2 * p + 1];
-            if (i < 0 || j < 0 || i >= s.n_taxa || j >= s.n_taxa || i == j)
-                return set_err(nullptr, PU_E_ARG, "%s: pair %lld = (%d, %d) of %d taxa", fn,
-                               (long long)p, i, j, s.n_taxa);
-        }
-    return PU_OK;
-}
-
-int check_codes(const char *fn, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes) {
-    for (int64_t i = 0; i < (int64_t)n_taxa * n_sites; ++i)
-        if (codes[i] >= n_codes)
-            return set_err(nullptr, PU_E_ARG, "%s: taxon %lld site %lld: code %d >= n_codes = %d",
-                           fn, (long long)(i / n_sites), (long long)(i % n_sites), (int)codes[i],
-                           n_codes);
-    return PU_OK;
-}
 
 struct ModelIn {
     int K, C;
@@ -433,12 +367,36 @@ int64_t seg_sites(int64_t S) {
 // pairs per chunk: count matrices and slabs within kDistWsBytes, or PU_DIST_CHUNK
 int64_t pair_chunk(int n_codes, int n_seg, int64_t n_pairs) {
     const size_t per = (size_t)n_codes * n_codes * 8 * (size_t)(1 + (n_seg > 1 ? n_seg : 0));
-    int64_t chunk = std::max<int64_t>(1, (int64_t)(kDistWsBytes / per));
-    if (const char *env = getenv("PU_DIST_CHUNK")) {
-        const long long v = atoll(env);
-        if (v > 0) chunk = std::min<int64_t>(chunk, v);
-    }
-    return std::min(chunk, n_pairs);
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)(kDistWsBytes / per));
+    return std::min(env_cap("PU_DIST_CHUNK", chunk), n_pairs);
+}
+
+// the model packed into the state's buffer, uploaded on st, and what k_pair_newton's arguments
+// take from it and from the options; counts, t0, out5 and n_pairs are the launch's own
+int newton_args(DistState &D, hipStream_t st, const ModelIn &m, int n, const Opt &o,
+                NewtonPairArgs *q) {
+    q->flat = pack_model(m, n, D.h_model);
+    if (int rc = D.model.reserve(D.h_model.size())) return rc;
+    HIPCHK(nullptr, hipMemcpyAsync(D.model.p, D.h_model.data(), D.h_model.size() * 8,
+                                   hipMemcpyHostToDevice, st));
+    q->model = D.model.p;
+    q->t0 = nullptr;
+    q->n_codes = n;
+    q->C = m.C;
+    q->lo = o.lo;
+    q->hi = o.hi;
+    q->tol = o.tol;
+    q->max_iter = o.max_iter;
+    return PU_OK;
+}
+
+int launch_newton(const NewtonPairArgs &q, int K, hipStream_t st) {
+    const dim3 grid((unsigned)((q.n_pairs + kNW - 1) / kNW));
+    if (K == 2) hipLaunchKernelGGL(k_pair_newton<2>, grid, dim3(64 * kNW), 0, st, q);
+    else if (K == 4) hipLaunchKernelGGL(k_pair_newton<4>, grid, dim3(64 * kNW), 0, st, q);
+    else hipLaunchKernelGGL(k_pair_newton<20>, grid, dim3(64 * kNW), 0, st, q);
+    HIPCHK(nullptr, hipGetLastError());
+    return PU_OK;
 }
 
 // the work of every pair call, queued on st: counts of each chunk of pairs into the state's
@@ -448,117 +406,63 @@ int run_pairs(int device, hipStream_t st, const Shape &s, const uint8_t *d_codes
               const double *d_w, const ModelIn *m, const Opt *o, double *d_out5,
               double *counts_host) {
     DistState &D = g_dist[device];
-    std::lock_guard<std::mutex> lk(D.mu);
-    if (D.done) HIPCHK(nullptr, hipEventSynchronize(D.done));
-    else HIPCHK(nullptr, hipEventCreateWithFlags(&D.done, hipEventDisableTiming));
-    const int n = s.n_codes, nb = n * n;
-    // the pair list
-    D.h_pairs.resize(2 * (size_t)s.n_pairs);
-    if (s.pairs) std::copy(s.pairs, s.pairs + 2 * s.n_pairs, D.h_pairs.begin());
-    else {
-        size_t k = 0;
-        for (int i = 0; i < s.n_taxa; ++i)
-            for (int j = i + 1; j < s.n_taxa; ++j) {
-                D.h_pairs[k++] = i;
-                D.h_pairs[k++] = j;
-            }
-    }
+    StateScope scope(D, st);
     int rc;
-    if ((rc = grow(&D.d_pairs, &D.pairs_cap, D.h_pairs.size()))) return rc;
-    HIPCHK(nullptr, hipMemcpyAsync(D.d_pairs, D.h_pairs.data(), D.h_pairs.size() * 4,
-                                   hipMemcpyHostToDevice, st));
-    uint32_t flat = 0;
+    if ((rc = scope.rc)) return rc;
+    const int n = s.n_codes, nb = n * n;
+    if ((rc = D.pairs.upload(st, s.n_taxa, s.n_pairs, s.pairs))) return rc;
+    NewtonPairArgs q;
     if (m) {
-        flat = pack_model(*m, n, D.h_model);
-        if ((rc = grow(&D.d_model, &D.model_cap, D.h_model.size()))) return rc;
-        HIPCHK(nullptr, hipMemcpyAsync(D.d_model, D.h_model.data(), D.h_model.size() * 8,
-                                       hipMemcpyHostToDevice, st));
+        if ((rc = newton_args(D, st, *m, n, *o, &q))) return rc;
         if (o->t0) {
             D.h_t0.assign(o->t0, o->t0 + s.n_pairs);
-            if ((rc = grow(&D.d_t0, &D.t0_cap, D.h_t0.size()))) return rc;
-            HIPCHK(nullptr, hipMemcpyAsync(D.d_t0, D.h_t0.data(), D.h_t0.size() * 8,
+            if ((rc = D.t0.reserve(D.h_t0.size()))) return rc;
+            HIPCHK(nullptr, hipMemcpyAsync(D.t0.p, D.h_t0.data(), D.h_t0.size() * 8,
                                            hipMemcpyHostToDevice, st));
         }
     }
     const int64_t seg = seg_sites(s.n_sites);
     const int n_seg = (int)((s.n_sites + seg - 1) / seg);
     const int64_t chunk = pair_chunk(n, n_seg, s.n_pairs);
-    if ((rc = grow(&D.d_counts, &D.counts_cap, (size_t)chunk * nb))) return rc;
-    if (n_seg > 1 && (rc = grow(&D.d_slabs, &D.slabs_cap, (size_t)n_seg * chunk * nb))) return rc;
+    if ((rc = D.counts.reserve((size_t)chunk * nb))) return rc;
+    if (n_seg > 1 && (rc = D.slabs.reserve((size_t)n_seg * chunk * nb))) return rc;
     const int P = (int)std::min<size_t>(64, kCountLds / ((size_t)bin_stride(n) * 8 + 2 * kRow));
-    const int64_t n_chunks = (s.n_pairs + chunk - 1) / chunk;
-    D.n_ev = 0;
-    if (D.profile)
-        while ((int64_t)D.ev.size() < 3 * n_chunks) {
-            hipEvent_t e;
-            HIPCHK(nullptr, hipEventCreate(&e));
-            D.ev.push_back(e);
-        }
+    if ((rc = D.prof.reserve((s.n_pairs + chunk - 1) / chunk))) return rc;
     for (int64_t p0 = 0; p0 < s.n_pairs; p0 += chunk) {
         const int64_t np = std::min(chunk, s.n_pairs - p0);
-        if (D.profile) HIPCHK(nullptr, hipEventRecord(D.ev[D.n_ev], st));
+        if ((rc = D.prof.mark(0, st))) return rc;
         CountArgs a;
         a.codes = d_codes;
         a.ld = ld;
         a.S = s.n_sites;
         a.w = d_w;
-        a.pairs = D.d_pairs + 2 * p0;
+        a.pairs = D.pairs.d.p + 2 * p0;
         a.n_pairs = np;
         a.n_codes = n;
         a.P = P;
         a.seg = seg;
-        a.out = n_seg > 1 ? D.d_slabs : D.d_counts;
+        a.out = n_seg > 1 ? D.slabs.p : D.counts.p;
         const dim3 grid((unsigned)((np + P - 1) / P), (unsigned)n_seg);
         hipLaunchKernelGGL(k_pair_counts, grid, dim3(64), count_lds(n, P), st, a);
         HIPCHK(nullptr, hipGetLastError());
         if (n_seg > 1) {
             const size_t ne = (size_t)np * nb;
             hipLaunchKernelGGL(k_pair_merge, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
-                               D.d_slabs, n_seg, ne, D.d_counts);
+                               D.slabs.p, n_seg, ne, D.counts.p);
             HIPCHK(nullptr, hipGetLastError());
         }
-        if (D.profile) HIPCHK(nullptr, hipEventRecord(D.ev[D.n_ev + 1], st));
+        if ((rc = D.prof.mark(1, st))) return rc;
         if (m) {
-            NewtonPairArgs q;
-            q.model = D.d_model;
-            q.counts = D.d_counts;
-            q.t0 = o->t0 ? D.d_t0 + p0 : nullptr;
+            q.counts = D.counts.p;
+            q.t0 = o->t0 ? D.t0.p + p0 : nullptr;
             q.out5 = d_out5 + 5 * p0;
             q.n_pairs = np;
-            q.n_codes = n;
-            q.C = m->C;
-            q.flat = flat;
-            q.lo = o->lo;
-            q.hi = o->hi;
-            q.tol = o->tol;
-            q.max_iter = o->max_iter;
-            const dim3 g2((unsigned)((np + kNW - 1) / kNW));
-            if (m->K == 2) hipLaunchKernelGGL(k_pair_newton<2>, g2, dim3(64 * kNW), 0, st, q);
-            else if (m->K == 4) hipLaunchKernelGGL(k_pair_newton<4>, g2, dim3(64 * kNW), 0, st, q);
-            else hipLaunchKernelGGL(k_pair_newton<20>, g2, dim3(64 * kNW), 0, st, q);
-            HIPCHK(nullptr, hipGetLastError());
+            if ((rc = launch_newton(q, m->K, st))) return rc;
         } else {
-            HIPCHK(nullptr, hipMemcpyAsync(counts_host + (size_t)p0 * nb, D.d_counts,
+            HIPCHK(nullptr, hipMemcpyAsync(counts_host + (size_t)p0 * nb, D.counts.p,
                                            (size_t)np * nb * 8, hipMemcpyDeviceToHost, st));
         }
-        if (D.profile) {
-            HIPCHK(nullptr, hipEventRecord(D.ev[D.n_ev + 2], st));
-            D.n_ev += 3;
-        }
-    }
-    HIPCHK(nullptr, hipEventRecord(D.done, st));
-    return PU_OK;
-}
-
-// host codes and weights onto the device (freed by the caller), on st
-int upload(hipStream_t st, const uint8_t *codes, size_t n_codes_bytes, const double *w, size_t n_w,
-           uint8_t **d_codes, double **d_w) {
-    int rc;
-    if ((rc = dalloc(nullptr, d_codes, n_codes_bytes))) return rc;
-    HIPCHK(nullptr, hipMemcpyAsync(*d_codes, codes, n_codes_bytes, hipMemcpyHostToDevice, st));
-    if (w) {
-        if ((rc = dalloc(nullptr, d_w, n_w))) return rc;
-        HIPCHK(nullptr, hipMemcpyAsync(*d_w, w, n_w * 8, hipMemcpyHostToDevice, st));
+        if ((rc = D.prof.mark(2, st))) return rc;
     }
     return PU_OK;
 }
@@ -585,37 +489,21 @@ int pair_newton_device(int device, hipStream_t st, const PairModel &pm, double l
                        double tol, int max_iter, const double *d_counts, int64_t n_batch,
                        int64_t rows, double *d_out5, int64_t out_stride) {
     DistState &D = g_dist[device];
-    std::lock_guard<std::mutex> lk(D.mu);
-    if (D.done) HIPCHK(nullptr, hipEventSynchronize(D.done));
-    else HIPCHK(nullptr, hipEventCreateWithFlags(&D.done, hipEventDisableTiming));
+    StateScope scope(D, st);
+    int rc;
+    if ((rc = scope.rc)) return rc;
     const ModelIn m{pm.K, pm.C, pm.table, pm.evecs, pm.evals, pm.ivecs, pm.freqs, pm.rates, pm.cw};
     const int n = pm.n_codes;
     NewtonPairArgs q;
-    q.flat = pack_model(m, n, D.h_model);
-    if (int rc = grow(&D.d_model, &D.model_cap, D.h_model.size())) return rc;
-    HIPCHK(nullptr, hipMemcpyAsync(D.d_model, D.h_model.data(), D.h_model.size() * 8,
-                                   hipMemcpyHostToDevice, st));
-    q.model = D.d_model;
-    q.t0 = nullptr;
-    q.n_codes = n;
-    q.C = m.C;
-    q.lo = lo;
-    q.hi = hi;
-    q.tol = tol;
-    q.max_iter = max_iter;
+    if ((rc = newton_args(D, st, m, n, Opt{nullptr, lo, hi, tol, max_iter}, &q))) return rc;
     const bool one = out_stride == rows;  // the rows of all batches are one list
-    const int64_t n_launch = one ? 1 : n_batch, per = one ? n_batch * rows : rows;
+    const int64_t n_launch = one ? 1 : n_batch;
+    q.n_pairs = one ? n_batch * rows : rows;
     for (int64_t b = 0; b < n_launch; ++b) {
         q.counts = d_counts + (size_t)b * rows * n * n;
         q.out5 = d_out5 + 5 * b * out_stride;
-        q.n_pairs = per;
-        const dim3 g2((unsigned)((per + kNW - 1) / kNW));
-        if (m.K == 2) hipLaunchKernelGGL(k_pair_newton<2>, g2, dim3(64 * kNW), 0, st, q);
-        else if (m.K == 4) hipLaunchKernelGGL(k_pair_newton<4>, g2, dim3(64 * kNW), 0, st, q);
-        else hipLaunchKernelGGL(k_pair_newton<20>, g2, dim3(64 * kNW), 0, st, q);
-        HIPCHK(nullptr, hipGetLastError());
+        if ((rc = launch_newton(q, m.K, st))) return rc;
     }
-    HIPCHK(nullptr, hipEventRecord(D.done, st));
     return PU_OK;
 }
 
@@ -626,27 +514,21 @@ extern "C" {
 int pu_pair_counts(int device, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes,
                    const double *site_weights, int64_t n_pairs, const int32_t *pairs,
                    double *counts_out) {
-    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs};
+    const char *fn = "pu_pair_counts";
+    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs, 1};
     int rc;
-    if ((rc = check_shape("pu_pair_counts", s, codes))) return rc;
-    if (!counts_out) return set_err(nullptr, PU_E_ARG, "pu_pair_counts: null output");
-    if ((rc = check_codes("pu_pair_counts", codes, n_taxa, n_sites, n_codes))) return rc;
+    if ((rc = check_shape(fn, s, !codes))) return rc;
+    if (!counts_out) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
+    if ((rc = check_codes(fn, codes, n_taxa, n_sites, n_codes))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    double *unused;
-    hipStream_t st;
-    if ((rc = ws_get(device, 1, &unused, &st))) return rc;
-    uint8_t *d_codes = nullptr;
-    double *d_w = nullptr;
-    rc = upload(st, codes, (size_t)n_taxa * n_sites, site_weights, (size_t)n_sites, &d_codes, &d_w);
-    if (!rc) rc = run_pairs(device, st, s, d_codes, n_sites, d_w, nullptr, nullptr, nullptr,
-                            counts_out);
-    if (!rc && hipStreamSynchronize(st) != hipSuccess)
-        rc = set_err(nullptr, PU_E_HIP, "pu_pair_counts: %s", hipGetErrorString(hipGetLastError()));
-    dfree(d_codes);
-    dfree(d_w);
-    return rc;
+    HostCall h(device);
+    const uint8_t *d_codes = h.to_device(codes, (size_t)n_taxa * n_sites);
+    const double *d_w = h.to_device(site_weights, (size_t)n_sites);
+    if (!h.rc)
+        h.rc = run_pairs(device, h.st, s, d_codes, n_sites, d_w, nullptr, nullptr, nullptr,
+                         counts_out);
+    return h.finish(fn);
 }
 
 int pu_pair_distances_device(int device, void *stream, int n_states, int n_cat, int n_codes,
@@ -657,11 +539,11 @@ int pu_pair_distances_device(int device, void *stream, int n_states, int n_cat, 
                              int64_t n_pairs, const int32_t *pairs, const double *t0, double lo,
                              double hi, double tol, int max_iter, double *d_out5) {
     const char *fn = "pu_pair_distances_device";
-    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs};
+    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs, 1};
     const ModelIn m{n_states, n_cat, code_table, evecs, evals, ivecs, freqs, rates, cat_weights};
     const Opt o{t0, lo, hi, tol, max_iter};
     int rc;
-    if ((rc = check_shape(fn, s, d_codes))) return rc;
+    if ((rc = check_shape(fn, s, !d_codes))) return rc;
     if (!d_out5) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
     if (ld < n_sites)
         return set_err(nullptr, PU_E_ARG, "%s: row stride %lld below n_sites = %lld", fn,
@@ -681,65 +563,29 @@ int pu_pair_distances(int device, int n_states, int n_cat, int n_codes, const do
                       const double *t0, double lo, double hi, double tol, int max_iter,
                       double *out5) {
     const char *fn = "pu_pair_distances";
-    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs};
+    const Shape s{n_taxa, n_codes, n_sites, n_pairs, pairs, 1};
     const ModelIn m{n_states, n_cat, code_table, evecs, evals, ivecs, freqs, rates, cat_weights};
     const Opt o{t0, lo, hi, tol, max_iter};
     int rc;
-    if ((rc = check_shape(fn, s, codes))) return rc;
+    if ((rc = check_shape(fn, s, !codes))) return rc;
     if (!out5) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
     if ((rc = check_model(fn, m, o, n_pairs))) return rc;
     if ((rc = check_codes(fn, codes, n_taxa, n_sites, n_codes))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    double *unused;
-    hipStream_t st;
-    if ((rc = ws_get(device, 1, &unused, &st))) return rc;
-    uint8_t *d_codes = nullptr;
-    double *d_w = nullptr, *d_out = nullptr;
-    rc = upload(st, codes, (size_t)n_taxa * n_sites, site_weights, (size_t)n_sites, &d_codes, &d_w);
-    if (!rc) rc = dalloc(nullptr, &d_out, 5 * (size_t)n_pairs);
-    if (!rc) rc = run_pairs(device, st, s, d_codes, n_sites, d_w, &m, &o, d_out, nullptr);
-    if (!rc) {
-        hipError_t e = hipMemcpyAsync(out5, d_out, 5 * (size_t)n_pairs * 8, hipMemcpyDeviceToHost,
-                                      st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = set_err(nullptr, PU_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    }
-    dfree(d_codes);
-    dfree(d_w);
-    dfree(d_out);
-    return rc;
+    HostCall h(device);
+    const uint8_t *d_codes = h.to_device(codes, (size_t)n_taxa * n_sites);
+    const double *d_w = h.to_device(site_weights, (size_t)n_sites);
+    double *d_out = h.alloc<double>(5 * (size_t)n_pairs);
+    if (!h.rc) h.rc = run_pairs(device, h.st, s, d_codes, n_sites, d_w, &m, &o, d_out, nullptr);
+    h.to_host(out5, d_out, 5 * (size_t)n_pairs);
+    return h.finish(fn);
 }
 
-int pu_pair_profile(int device, int on) {
-    if (device < 0 || device >= 64) return set_err(nullptr, PU_E_ARG, "device %d", device);
-    DistState &D = g_dist[device];
-    std::lock_guard<std::mutex> lk(D.mu);
-    D.profile = on != 0;
-    D.n_ev = 0;
-    return PU_OK;
-}
+int pu_pair_profile(int device, int on) { return profile_set(g_dist, device, on); }
 
 int pu_pair_kernel_ms(int device, double *counts_ms, double *newton_ms) {
-    if (device < 0 || device >= 64 || !counts_ms || !newton_ms)
-        return set_err(nullptr, PU_E_ARG, "pu_pair_kernel_ms: bad argument");
-    DistState &D = g_dist[device];
-    std::lock_guard<std::mutex> lk(D.mu);
-    if (!D.n_ev) return set_err(nullptr, PU_E_STATE, "pu_pair_kernel_ms: nothing recorded");
-    DeviceGuard g(device);
-    HIPCHK(nullptr, hipEventSynchronize(D.ev[D.n_ev - 1]));
-    double c = 0.0, w = 0.0;
-    for (int i = 0; i < D.n_ev; i += 3) {
-        float a = 0.f, b = 0.f;
-        HIPCHK(nullptr, hipEventElapsedTime(&a, D.ev[i], D.ev[i + 1]));
-        HIPCHK(nullptr, hipEventElapsedTime(&b, D.ev[i + 1], D.ev[i + 2]));
-        c += a;
-        w += b;
-    }
-    *counts_ms = c;
-    *newton_ms = w;
-    return PU_OK;
+    return profile_ms("pu_pair_kernel_ms", g_dist, device, counts_ms, newton_ms);
 }
 
 }  // extern "C"

@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "pu_ctx.h"
+#include "pu_service.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "pu_nj.hip: gfx950 only, as the other kernel files of this library"
@@ -434,19 +435,21 @@ __global__ void k_nj_last(MemState s, NjOut out, int64_t mat) {
 
 // ---- scatter ------------------------------------------------------------------------------
 
-// without a pair list: one thread per matrix entry, pair (i, j), i < j, is row
-// i n - i (i + 1) / 2 + j - i - 1 of out5; the diagonal is zero
+// without a pair list: one thread per matrix entry of every matrix of the batch; pair (i, j),
+// i < j, is row i n - i (i + 1) / 2 + j - i - 1 of the matrix's out5 rows; the diagonal is zero
 __global__ void __launch_bounds__(256)
-    k_pair_matrix_all(int n, const double *__restrict__ out5, double *__restrict__ D, int64_t ld) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)n * n) return;
-    const int i = (int)(e / n), j = (int)(e - (int64_t)i * n);
+    k_pair_matrix_all(int n_mat, int n, const double *__restrict__ out5, double *__restrict__ D,
+                      int64_t ld) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x, nn = (int64_t)n * n;
+    if (e >= nn * n_mat) return;
+    const int64_t r = e / nn, k = e - r * nn;
+    const int i = (int)(k / n), j = (int)(k - (int64_t)i * n);
     double d = 0.0;
     if (i != j) {
-        const int64_t lo = min(i, j), hi = max(i, j);
-        d = out5[5 * (lo * n - lo * (lo + 1) / 2 + hi - lo - 1)];
+        const int64_t lo = min(i, j), hi = max(i, j), np = (nn - n) / 2;
+        d = out5[5 * (r * np + lo * n - lo * (lo + 1) / 2 + hi - lo - 1)];
     }
-    D[(int64_t)i * ld + j] = d;
+    D[(r * n + i) * ld + j] = d;
 }
 
 // with a pair list: both entries of every listed pair; nothing else is written
@@ -463,36 +466,13 @@ __global__ void __launch_bounds__(256)
 
 // ---- host side ---------------------------------------------------------------------------
 
-// per-device buffers (grown, never shrunk), guarded by mu; `done` marks the end of the last
-// call's queued work, which the next call waits for before it touches them
-struct NjState {
-    std::mutex mu;
-    double *d_ws = nullptr;
-    size_t ws_cap = 0;
-    int32_t *d_iw = nullptr;
-    size_t iw_cap = 0;
-    int32_t *d_pairs = nullptr;
-    size_t pairs_cap = 0;
-    std::vector<int32_t> h_pairs;
-    hipEvent_t done = nullptr;
+// per-device buffers of tier B and of the scatter (DevState: pu_service.h)
+struct NjState : DevState {
+    DevBuf<double> ws;
+    DevBuf<int32_t> iw;
+    PairList pairs;
 };
 NjState g_nj[64];
-
-template <class T>
-int grow(T **p, size_t *cap, size_t n) {
-    if (*cap >= n) return PU_OK;
-    dfree(*p);
-    *cap = 0;
-    if (int rc = dalloc(nullptr, p, n)) return rc;
-    *cap = n;
-    return PU_OK;
-}
-
-int begin(NjState &S) {
-    if (S.done) HIPCHK(nullptr, hipEventSynchronize(S.done));
-    else HIPCHK(nullptr, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-    return PU_OK;
-}
 
 int check_nj(const char *fn, int method, int n_mat, int n, const void *D, int64_t ld,
              const NjOut &o) {
@@ -521,8 +501,8 @@ bool use_lds(int n, int method) {
 int run_nj(int device, hipStream_t st, int method, int n_mat, int n, const double *d_D,
            int64_t ld, const NjOut &o) {
     NjState &S = g_nj[device];
-    std::lock_guard<std::mutex> lk(S.mu);
-    if (int rc = begin(S)) return rc;
+    StateScope scope(S, st);
+    if (scope.rc) return scope.rc;
     if (use_lds(n, method)) {
         LdsArgs a{d_D, ld, n, o};
         const size_t lds = nj_lds_bytes(n, method);
@@ -532,19 +512,19 @@ int run_nj(int device, hipStream_t st, int method, int n_mat, int n, const doubl
     } else {
         const size_t nn = (size_t)n * n;
         int rc;
-        if ((rc = grow(&S.d_ws, &S.ws_cap, (size_t)(1 + method) * (nn + n) + kMaxPart))) return rc;
-        if ((rc = grow(&S.d_iw, &S.iw_cap, (size_t)3 * n + kMaxPart))) return rc;
+        if ((rc = S.ws.reserve((size_t)(1 + method) * (nn + n) + kMaxPart))) return rc;
+        if ((rc = S.iw.reserve((size_t)3 * n + kMaxPart))) return rc;
         MemState s;
         s.n = n;
-        s.D = S.d_ws;
+        s.D = S.ws.p;
         s.V = method ? s.D + nn : s.D;
-        s.R = S.d_ws + (size_t)(1 + method) * nn;
+        s.R = S.ws.p + (size_t)(1 + method) * nn;
         s.RV = method ? s.R + n : s.R;
         s.pq = s.R + (size_t)(1 + method) * n;
-        s.live[0] = S.d_iw;
-        s.live[1] = S.d_iw + n;
-        s.id = S.d_iw + 2 * (size_t)n;
-        s.pk = reinterpret_cast<uint32_t *>(S.d_iw + 3 * (size_t)n);
+        s.live[0] = S.iw.p;
+        s.live[1] = S.iw.p + n;
+        s.id = S.iw.p + 2 * (size_t)n;
+        s.pk = reinterpret_cast<uint32_t *>(S.iw.p + 3 * (size_t)n);
         for (int64_t mat = 0; mat < n_mat; ++mat) {
             hipLaunchKernelGGL(k_nj_copy, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, s,
                                method, d_D + mat * n * ld, ld);
@@ -566,11 +546,19 @@ int run_nj(int device, hipStream_t st, int method, int n_mat, int n, const doubl
             HIPCHK(nullptr, hipGetLastError());
         }
     }
-    HIPCHK(nullptr, hipEventRecord(S.done, st));
     return PU_OK;
 }
 
 }  // namespace
+
+int pu::pair_matrix_all(hipStream_t st, int n_mat, int n, const double *d_out5, double *d_D,
+                        int64_t ld) {
+    const int64_t ne = (int64_t)n_mat * n * n;
+    hipLaunchKernelGGL(k_pair_matrix_all, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
+                       n_mat, n, d_out5, d_D, ld);
+    HIPCHK(nullptr, hipGetLastError());
+    return PU_OK;
+}
 
 extern "C" {
 
@@ -606,43 +594,22 @@ int pu_nj(int device, int method, int n_mat, int n, const double *D, int32_t *jo
             }
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
-    std::lock_guard<std::mutex> lk(ws_mutex(device));
-    double *unused;
-    hipStream_t st;
-    if ((rc = ws_get(device, 1, &unused, &st))) return rc;
+    HostCall h(device);
     const size_t nD = (size_t)n_mat * n * n, nj = (size_t)n_mat * (n - 2) * 2;
     const size_t nq = (size_t)n_mat * (n - 3);
-    double *d_D = nullptr, *d_f = nullptr;  // d_f: lens, root_len, q
-    int32_t *d_i = nullptr;                 // joins, root
-    rc = dalloc(nullptr, &d_D, nD);
-    if (!rc) rc = dalloc(nullptr, &d_f, nj + n_mat + nq);
-    if (!rc) rc = dalloc(nullptr, &d_i, nj + 2 * (size_t)n_mat);
-    if (!rc) {
+    const double *d_D = h.to_device(D, nD);
+    double *d_f = h.alloc<double>(nj + n_mat + nq);          // lens, root_len, q
+    int32_t *d_i = h.alloc<int32_t>(nj + 2 * (size_t)n_mat);  // joins, root
+    if (!h.rc) {
         const NjOut o{d_i, d_f, d_i + nj, d_f + nj, q_out && nq ? d_f + nj + n_mat : nullptr};
-        hipError_t e = hipMemcpyAsync(d_D, D, nD * 8, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) rc = set_err(nullptr, PU_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-        if (!rc) rc = run_nj(device, st, method, n_mat, n, d_D, n, o);
-        if (!rc) {
-            e = hipMemcpyAsync(joins_out, o.joins, nj * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(lens_out, o.lens, nj * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(root_out, o.root, (size_t)n_mat * 2 * 4, hipMemcpyDeviceToHost,
-                                   st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(root_len_out, o.root_len, (size_t)n_mat * 8,
-                                   hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && o.q)
-                e = hipMemcpyAsync(q_out, o.q, nq * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess)
-                rc = set_err(nullptr, PU_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-        }
+        h.rc = run_nj(device, h.st, method, n_mat, n, d_D, n, o);
+        h.to_host(joins_out, o.joins, nj);
+        h.to_host(lens_out, o.lens, nj);
+        h.to_host(root_out, o.root, (size_t)n_mat * 2);
+        h.to_host(root_len_out, o.root_len, (size_t)n_mat);
+        if (o.q) h.to_host(q_out, o.q, nq);
     }
-    dfree(d_D);
-    dfree(d_f);
-    dfree(d_i);
-    return rc;
+    return h.finish(fn);
 }
 
 int pu_pair_matrix_device(int device, void *stream, int n_taxa, int64_t n_pairs,
@@ -655,38 +622,19 @@ int pu_pair_matrix_device(int device, void *stream, int n_taxa, int64_t n_pairs,
     if (ld < n_taxa)
         return set_err(nullptr, PU_E_ARG, "%s: row stride %lld below n_taxa = %d", fn,
                        (long long)ld, n_taxa);
-    const int64_t all = (int64_t)n_taxa * (n_taxa - 1) / 2;
-    if (n_pairs < 1 || (!pairs && n_pairs != all))
-        return set_err(nullptr, PU_E_ARG, "%s: n_pairs = %lld (without a pair list: all %lld)", fn,
-                       (long long)n_pairs, (long long)all);
-    if (pairs)
-        for (int64_t p = 0; p < n_pairs; ++p) {
-            const int i = pairs[2 * p], j = pairs[2 * p + 1];
-            if (i < 0 || j < 0 || i >= n_taxa || j >= n_taxa || i == j)
-                return set_err(nullptr, PU_E_ARG, "%s: pair %lld = (%d, %d) of %d taxa", fn,
-                               (long long)p, i, j, n_taxa);
-        }
     int rc;
+    if ((rc = check_pairs(fn, n_taxa, n_pairs, pairs))) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
     hipStream_t st = (hipStream_t)stream;
     NjState &S = g_nj[device];
-    std::lock_guard<std::mutex> lk(S.mu);
-    if ((rc = begin(S))) return rc;
-    if (!pairs) {
-        const int64_t nn = (int64_t)n_taxa * n_taxa;
-        hipLaunchKernelGGL(k_pair_matrix_all, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st,
-                           n_taxa, d_out5, d_D, ld);
-    } else {
-        S.h_pairs.assign(pairs, pairs + 2 * n_pairs);
-        if ((rc = grow(&S.d_pairs, &S.pairs_cap, S.h_pairs.size()))) return rc;
-        HIPCHK(nullptr, hipMemcpyAsync(S.d_pairs, S.h_pairs.data(), S.h_pairs.size() * 4,
-                                       hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pair_matrix_list, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256),
-                           0, st, n_pairs, S.d_pairs, d_out5, d_D, ld);
-    }
+    StateScope scope(S, st);
+    if ((rc = scope.rc)) return rc;
+    if (!pairs) return pair_matrix_all(st, 1, n_taxa, d_out5, d_D, ld);
+    if ((rc = S.pairs.upload(st, n_taxa, n_pairs, pairs))) return rc;
+    hipLaunchKernelGGL(k_pair_matrix_list, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0,
+                       st, n_pairs, S.pairs.d.p, d_out5, d_D, ld);
     HIPCHK(nullptr, hipGetLastError());
-    HIPCHK(nullptr, hipEventRecord(S.done, st));
     return PU_OK;
 }
 

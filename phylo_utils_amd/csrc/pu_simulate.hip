@@ -45,6 +45,7 @@
 
 #include "pu_ctx.h"
 #include "pu_philox.h"
+#include "pu_service.h"
 
 // Built, tested and measured on gfx950 only (wave64, the launch shapes below).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -392,37 +393,21 @@ int pu_simulate(pu_ctx *c, uint64_t seed, int64_t first_site, int64_t n_sites, u
     if (int rc = sim_check(c, first_site, n_sites, tips_out, n_sites, nullptr, 0)) return rc;
     DeviceGuard g(c->device);
     const size_t n = (size_t)n_sites, nt = (size_t)c->n_tips * n, nv = (size_t)c->n_nodes * n;
-    uint8_t *d_t = nullptr, *d_c = nullptr, *d_n = nullptr;
-    int rc = dalloc(&c->err, &d_t, nt);
-    if (!rc && cats_out) rc = dalloc(&c->err, &d_c, n);
-    if (!rc && nodes_out) rc = dalloc(&c->err, &d_n, nv);
-    auto done = [&](int code) {
-        dfree(d_t);
-        dfree(d_c);
-        dfree(d_n);
-        return code;
-    };
-    if (rc) return done(rc);
+    HostCall h(c->stream, &c->err);
+    uint8_t *d_t = h.alloc<uint8_t>(nt);
+    uint8_t *d_c = cats_out ? h.alloc<uint8_t>(n) : nullptr;
+    uint8_t *d_n = nodes_out ? h.alloc<uint8_t>(nv) : nullptr;
     // a declared tip that the schedule does not reach keeps state 0
-    hipError_t e = hipMemsetAsync(d_t, 0, nt, c->stream);
-    if (e == hipSuccess && d_n) e = hipMemsetAsync(d_n, 0, nv, c->stream);
-    if (e != hipSuccess)
-        return done(set_err(&c->err, PU_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e)));
-    if ((rc = pu_simulate_device(c, seed, first_site, n_sites, d_t, n_sites, d_c, d_n, n_sites)))
-        return done(rc);
-    e = hipMemcpyAsync(tips_out, d_t, nt, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && cats_out)
-        e = hipMemcpyAsync(cats_out, d_c, n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && nodes_out)
-        e = hipMemcpyAsync(nodes_out, d_n, nv, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && cum_out)
-        e = hipMemcpyAsync(cum_out, c->sim->d_cum,
-                           (size_t)c->n_nodes * c->C * c->K * c->K * 8, hipMemcpyDeviceToHost,
-                           c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess)
-        return done(set_err(&c->err, PU_E_HIP, "pu_simulate: %s", hipGetErrorString(e)));
-    return done(PU_OK);
+    if (!h.rc) h.hip("hipMemsetAsync", hipMemsetAsync(d_t, 0, nt, h.st));
+    if (!h.rc && d_n) h.hip("hipMemsetAsync", hipMemsetAsync(d_n, 0, nv, h.st));
+    if (!h.rc)
+        h.rc = pu_simulate_device(c, seed, first_site, n_sites, d_t, n_sites, d_c, d_n, n_sites);
+    h.to_host(tips_out, d_t, nt);
+    if (cats_out) h.to_host(cats_out, d_c, n);
+    if (nodes_out) h.to_host(nodes_out, d_n, nv);
+    if (!h.rc && cum_out)
+        h.to_host(cum_out, c->sim->d_cum, (size_t)c->n_nodes * c->C * c->K * c->K);
+    return h.finish("pu_simulate");
 }
 
 int pu_evolve_states(int device, int K, int C, int64_t n_sites, uint64_t seed,

@@ -309,6 +309,31 @@ def test_device_form_equals_host_form_with_a_padded_stride():
     assert np.all(d_codes.cpu().numpy()[:, S:] == 255)
 
 
+def test_back_to_back_calls_on_two_streams():
+    """Two device calls with pair lists of different lengths on two streams and nothing between
+    them: the second waits for the first before it reuses the per-device buffers.  257 sites are
+    two count segments, so the slabs and the merge kernel are in play."""
+    import torch
+    codes = dna_codes(np.random.default_rng(257), 6, 257)
+    nt, S = codes.shape
+    model, rm = gtr(), GammaRateModel(4, 0.5)
+    lists = ([(0, 5), (4, 2), (3, 0)], None)
+    refs = [distance.evaluate_codes(codes, DNA_TABLE, model, rm, None, pr) for pr in lists]
+    assert [len(r) for r in refs] == [3, 15]
+    dev = torch.device("cuda", 0)
+    d_codes = torch.from_numpy(codes).to(dev)
+    outs = [torch.full((len(r), 5), -1.0, dtype=torch.float64, device=dev) for r in refs]
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    torch.cuda.synchronize(dev)  # the inputs are in place; from here on nothing waits
+    for st, pr, d_out in zip(streams, lists, outs):
+        distance.distances_device(st.cuda_stream, d_codes.data_ptr(), S, nt, S, DNA_TABLE, model,
+                                  rm, None, pr, d_out5=d_out.data_ptr())
+    for st in streams:
+        st.synchronize()
+    for d_out, ref in zip(outs, refs):
+        np.testing.assert_array_equal(d_out.cpu().numpy(), ref)
+
+
 # ---------------------------------------------------------------------------- pipeline
 NEWICK9 = ("(((a:0.05,b:0.05):0.1,c:0.2):0.1,((d:0.15,e:0.2):0.1,f:0.25):0.1,"
            "((g:0.04,h:0.06):0.15,i:0.3):0.1);")

@@ -130,6 +130,45 @@ def test_tiers_and_repeats_are_bitwise_equal(method, monkeypatch):
                 assert np.array_equal(x, y)
 
 
+def test_tier_b_batches_on_two_streams(monkeypatch):
+    """Tier B keeps its working copies in per-device buffers: two batches queued on two streams
+    with nothing between them give the bits each gives on one stream."""
+    import torch
+    monkeypatch.setenv("PU_NJ_TIER", "B")
+    n, B = 5, 2
+    dev = torch.device("cuda", 0)
+    batches = [np.stack([NR.random_matrix(50 + 2 * b + i, n) for i in range(B)]) for b in range(2)]
+    d_Ds = [torch.from_numpy(x).to(dev) for x in batches]
+
+    def outputs():
+        return [torch.zeros(shape, dtype=dt, device=dev)
+                for shape, dt in (((B, n - 2, 2), torch.int32), ((B, n - 2, 2), torch.float64),
+                                  ((B, 2), torch.int32), ((B,), torch.float64),
+                                  ((B, n - 3), torch.float64))]
+
+    def queue(stream, d_D, out, method):
+        nj.nj_device(stream.cuda_stream, d_D.data_ptr(), n, n, *[o.data_ptr() for o in out],
+                     method=method, n_mat=B)
+
+    for method in METHODS:
+        want = []
+        for d_D in d_Ds:  # one stream, one batch at a time
+            out = outputs()
+            queue(torch.cuda.current_stream(dev), d_D, out, method)
+            torch.cuda.synchronize(dev)
+            want.append([o.cpu().numpy() for o in out])
+        streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+        outs = [outputs(), outputs()]
+        torch.cuda.synchronize(dev)  # the outputs are zeroed; from here on nothing waits
+        for st, d_D, out in zip(streams, d_Ds, outs):
+            queue(st, d_D, out, method)
+        for st in streams:
+            st.synchronize()
+        for out, ref in zip(outs, want):
+            for x, y in zip(out, ref):
+                assert np.array_equal(x.cpu().numpy(), y), method
+
+
 # ---------------------------------------------------------------------------- device path
 def gtr():
     return SM.GTR(CFG2_GTR_RATES, CFG2_FREQS)
