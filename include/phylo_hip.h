@@ -230,6 +230,39 @@ int pu_optimise_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, 
  * machine.  The length x is stored (pu_get_branch_lengths). */
 int pu_minimise_edge(pu_ctx *ctx, int node_a, int node_b, int method, double lo, double t0,
                      double hi, double tol, double *out3);
+/* ---- nearest-neighbour interchange on resident partials ------------------ */
+/* The largest category count the quartet kernel takes for n_states = 2, 4 or 20 (its LDS use
+ * of one workgroup against the 160 KiB of a CU: 25, 24, 19); PU_E_ARG for other n_states.
+ * Host only. */
+int pu_quartet_max_cat(int n_states);
+/* out9[3][3] = {lnL, d1, d2} of arrangements 0..2 at central lengths t[3] (t NULL: all three at
+ * lens[4]); nodes[4] pairwise distinct; lens[5] = pendant lengths of nodes 0..3, then the
+ * standing central length.  Arrangement 0 is (x0,x1 | x2,x3), the standing one; 1 is
+ * (x0,x2 | x1,x3); 2 is (x0,x3 | x1,x2).  For (a,b | c,d): L = clv(P(l_a), P(l_b), a, b) and
+ * R = clv(P(l_c), P(l_d), c, d) with the engine's rescale rule, then what pu_edge_derivs
+ * defines for ends L, R at length t[k].  On the nodes' CURRENT partials, like pu_edge_lnl.
+ * Changes nothing in the context.  PU_KEEP_PARTIALS contexts on the device eigen-system
+ * without an ascertainment correction (else PU_E_STATE); PU_E_ARG: a null buffer, a node out
+ * of range, repeated nodes, a non-positive or non-finite length, more categories than
+ * pu_quartet_max_cat. */
+int pu_quartet_derivs(pu_ctx *ctx, const int32_t nodes[4], const double lens[5],
+                      const double *t, double *out9);
+/* One scoring pass over the optimising traversal (rows as pu_optimise_sweep takes them, lengths
+ * the context's current ones).  Every re-orientation / restore row is applied.  At every
+ * optimise row (.., NOD, PAR) whose NOD is internal, and at row 0 when both ends are internal,
+ * the quartet (children of NOD | SIB, GPA) is scored (row 0: the children of its second end
+ * for SIB, GPA).  For each arrangement the central length is optimised from the standing one
+ * with the library's own Newton rule (pu_optimise_edge's: safeguards, bounds [1e-8, 100],
+ * stopping rule), the three arrangements advancing together, one k_quartet launch per
+ * iteration.  scores_out [n_scored][3][4] = {t*, lnL(t*), lnL'(t*), evaluations}.
+ * quartets_out [n_scored][6] = {NOD, PAR, x0, x1, x2, x3}.  *n_scored_out <= n_tips - 3; the
+ * buffers hold n_tips - 3 entries.  No length is stored.  The pass ends with a full traversal,
+ * so the context's partials, lnL and sitewise lnL are bitwise those of pu_run before the call.
+ * PU_E_ARG also for tol <= 0 and max_iter < 0. */
+int pu_nni_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int max_iter,
+                 double *scores_out, int32_t *quartets_out, int *n_scored_out);
+/* HIP-event time (ms) of the last k_quartet launch made while pu_ctx_profile was on. */
+int pu_quartet_kernel_ms(pu_ctx *ctx, double *ms_out);
 /* Current lengths in pu_set_schedule's layout: brlens_out[n_ops][2], root length. */
 int pu_get_branch_lengths(pu_ctx *ctx, double *brlens_out, double *root_len_out);
 

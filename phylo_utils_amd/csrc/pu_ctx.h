@@ -216,6 +216,13 @@ struct pu_ctx {
     bool nt_fresh = false;
     std::vector<hipEvent_t> edge_ev;  // profiling: event pairs around edge reductions
     int n_edge_prof = 0;
+    // quartet scoring (pu_nni.hip): per-workgroup sums [q_tiles][9], the 9 results in mapped
+    // host memory, and the HIP-event time of the last k_quartet launch when profiling
+    double *d_q_part = nullptr;
+    int q_tiles = 0;
+    double *h_q_res = nullptr, *d_q_res_host = nullptr;
+    hipEvent_t q_ev[2] = {nullptr, nullptr};
+    float q_ms = 0.f;
 
     // Lewis ascertainment-bias correction (tree_model.py:92-98, 151-156, 209-214): mode 0 off,
     // 1 the reference's form, 2 weighted; the dummy invariant sites are [asc_first, S)
@@ -261,6 +268,14 @@ int refresh_host_p(pu_ctx *c);
 int ensure_host_p(pu_ctx *c);
 // pu_edge.cpp: release the edge-operation buffers of a context
 void edge_free(pu_ctx *c);
+// pu_edge.cpp, for pu_nni.hip: the edge calls' readiness checks and buffers (prepare), a
+// node's source, the key of edge (u, v) into up_len, the kernels' common arguments, and n
+// in-place updates (par, c1, c2) at lengths brlens[n][2], queued on the context's stream
+int edge_prepare(pu_ctx *c);
+int edge_node_src(pu_ctx *c, int node, NodeSrc *out);
+int edge_key(pu_ctx *c, int u, int v, int *key);
+void edge_fill_args(const pu_ctx *c, EdgeArgs &a);
+int edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens);
 // pu_simulate.hip: release the simulator's buffers of a context
 void sim_free(pu_ctx *c);
 // enqueue the ascertainment-bias correction of site_lnl and *lnl (no-op when off)

@@ -623,6 +623,15 @@ int update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens) {
 
 int pu::flush_lengths(pu_ctx *c) { return c->lengths_dirty ? push_lengths(c) : PU_OK; }
 
+// the edge layer's helpers for pu_nni.hip (quartet scoring on the same resident partials)
+int pu::edge_prepare(pu_ctx *c) { return prepare(c); }
+int pu::edge_node_src(pu_ctx *c, int node, NodeSrc *out) { return node_src(c, node, out); }
+int pu::edge_key(pu_ctx *c, int u, int v, int *key) { return edge_of(c, u, v, key); }
+void pu::edge_fill_args(const pu_ctx *c, EdgeArgs &a) { fill_args(c, a); }
+int pu::edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens) {
+    return update_ops(c, n, ops, brlens);
+}
+
 int pu::enqueue_ascbias(pu_ctx *c, double *lnl) {
     if (!c->asc_mode) return PU_OK;
     if (!c->d_asc_corr) {
@@ -667,6 +676,14 @@ void pu::edge_free(pu_ctx *c) {
         h = nullptr;
     }
     c->edge_tiles = 0;
+    dfree(c->d_q_part);
+    c->q_tiles = 0;
+    if (c->h_q_res) (void)hipHostFree(c->h_q_res);
+    c->h_q_res = nullptr;
+    for (hipEvent_t &e : c->q_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 extern "C" {

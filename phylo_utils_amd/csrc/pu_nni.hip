@@ -1,0 +1,499 @@
+// pu_nni.hip -- nearest-neighbour interchange on the device-resident CLVs of a context
+// (DESIGN 4.15): the gfx950 kernel that scores the three arrangements of a quartet of
+// subtrees, and its C ABI (include/phylo_hip.h):
+//   pu_quartet_max_cat   the kernel's category limit per alphabet (host only)
+//   pu_quartet_derivs    lnL, dlnL/dt, d2lnL/dt2 of the three arrangements of four nodes
+//   pu_nni_sweep         one pass of the optimising traversal that scores every internal edge,
+//                        the central length of each arrangement optimised by Newton
+//
+// Arrangement (a,b | c,d) of nodes x0..x3 with pendant lengths l0..l3 and central length t:
+//   L = clv(P(l_a), P(l_b), a, b), R = clv(P(l_c), P(l_d), c, d) -- the engine's update with
+//   its rescale rule (pu_edge_dev.h rescale) on the nodes' current partials and scalers --
+//   then what EDGE_DERIV (pu_edge.hip) defines for ends L, R at length t.
+//
+// Everything runs in the eigen-basis of the model, P(t r) = V diag(e^{lambda r t}) V^-1:
+//   y_i = V (e^{lambda r l_i} o (V^-1 x_i))           the four pendant products, shared by the
+//                                                     three arrangements, computed once
+//   c_k = [V^T (pi o L)]_k [V^-1 R]_k                 K coefficients per arrangement
+//   f = sum_k c_k e^{lambda_k r t}, f' = sum_k c_k (lambda_k r) e^{..}, f'' likewise
+// (the sum table of k_edge_newton), so no K x K transition matrix is ever built: LDS holds V,
+// V^-1 and 13 K exponentials per category, whatever the lengths.
+//
+// Mapping (k_edge's): a workgroup is one 64-site tile, a lane a site, wave w owns
+// rate categories w, w + nw, ...; the categories of a site meet in LDS, where wave k mixes
+// arrangement k exactly as k_edge mixes its edge.  Every workgroup writes its 9 sums; a
+// one-workgroup second launch adds them in a fixed order (k_edge_sum's), bitwise repeatable.
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "pu_ctx.h"
+#include "pu_edge_dev.h"
+
+using namespace pu;
+
+namespace {
+
+// MIN / MAX length of the optimisers (pu_edge.cpp kMinLen / kMaxLen)
+constexpr double kMinLen = 1e-8;
+constexpr double kMaxLen = 100.0;
+
+struct QuartetArgs {
+    NodeSrc x[4];
+    double l[4];   // pendant lengths
+    double t[3];   // central length of each arrangement
+    double *part;  // [grid][9] per-workgroup sums
+};
+
+// waves per workgroup at most: K = 20 holds four K-vectors and two more per arrangement in
+// registers (about 300 VGPRs), so one wave per SIMD
+__host__ __device__ constexpr int quartet_max_waves(int K) { return K == 20 ? 4 : 8; }
+__host__ __device__ inline int quartet_waves(int K, int C) {
+    return C < quartet_max_waves(K) ? C : quartet_max_waves(K);
+}
+
+// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][pendant
+// exponentials 4*C*K][central exponentials and their two derivative factors 3*3*C*K]
+// [per-(arrangement, category, site) f, f', f'', log scaler: 3*4*C*64]
+struct QuartetLds {
+    size_t evecs, ivecs, evals, pi, rates, ex, eg, vals, total;
+    __host__ __device__ QuartetLds(int K, int C) {
+        evecs = 0;
+        ivecs = evecs + (size_t)K * K;
+        evals = ivecs + (size_t)K * K;
+        pi = evals + K;
+        rates = pi + K;
+        ex = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+        eg = ex + (size_t)4 * C * K;
+        vals = eg + (size_t)9 * C * K;
+        total = vals + (size_t)12 * C * kLanes;
+    }
+};
+constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
+
+// the other two nodes of arrangement k = (x0, x_{k+1} | x_c, x_d)
+__host__ __device__ constexpr int arr_c(int k) { return k == 0 ? 2 : 1; }
+__host__ __device__ constexpr int arr_d(int k) { return k == 2 ? 2 : 3; }
+
+template <int K>
+__global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs a, QuartetArgs q) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int C = a.C;
+    const QuartetLds L(K, C);
+    const int tile = blockIdx.x, l = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int64_t site = (int64_t)tile * kLanes + l;
+    const int64_t site_c = site < a.S ? site : a.S - 1;
+    const double *ev = lds + L.evecs, *iv = lds + L.ivecs, *el = lds + L.evals,
+                 *pi = lds + L.pi, *rt = lds + L.rates, *ex = lds + L.ex, *eg = lds + L.eg;
+    double *vals = lds + L.vals;
+
+    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
+        lds[L.evecs + i] = a.evecs[i];
+        lds[L.ivecs + i] = a.ivecs[i];
+    }
+    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+        lds[L.evals + i] = a.evals[i];
+        lds[L.pi + i] = a.pi[i];
+    }
+    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    __syncthreads();
+    // e^{lambda (l r)} of the four pendant edges, build_p's arithmetic: [node][category][state]
+    for (int idx = threadIdx.x; idx < 4 * C * K; idx += blockDim.x) {
+        const int j = idx % K, ic = idx / K, c = ic % C, i = ic / C;
+        lds[L.ex + idx] = exp(el[j] * (q.l[i] * rt[c]));
+    }
+    // central edge of arrangement k: e, (lambda r) e, (lambda r)^2 e at [k][order][category][state]
+    for (int idx = threadIdx.x; idx < 3 * C * K; idx += blockDim.x) {
+        const int j = idx % K, kc = idx / K, c = kc % C, k = kc / C;
+        const double r = rt[c], x = el[j] * r;
+        const double e = exp(el[j] * (q.t[k] * r));
+        double *g = lds + L.eg + (size_t)3 * k * C * K + (size_t)c * K + j;
+        g[0] = e;
+        g[(size_t)C * K] = x * e;
+        g[(size_t)2 * C * K] = (x * x) * e;
+    }
+    __syncthreads();
+
+    // the loops over the eigen index run rolled for K = 20, so that the rows and columns of V
+    // and V^-1 are read from LDS where they are used (unrolled, they are hoisted and spill)
+    constexpr int kEigUnroll = K > 4 ? 1 : K;
+    for (int c = w; c < C; c += nw) {
+        // y_i = V (e o (V^-1 x_i)): the four pendant products of this (site, category)
+        double y[4][K], s[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double v[K];
+            node_vec<K>(a, q.x[i], c, tile, l, site_c, v, s[i]);
+            const double *e = ex + (size_t)(i * C + c) * K;
+#pragma unroll
+            for (int m = 0; m < K; ++m) y[i][m] = 0.0;
+#pragma unroll kEigUnroll
+            for (int j = 0; j < K; ++j) {
+                double u = 0.0;
+#pragma unroll
+                for (int m = 0; m < K; ++m) u = fma(iv[j * K + m], v[m], u);
+                u *= e[j];
+#pragma unroll
+                for (int m = 0; m < K; ++m) y[i][m] = fma(ev[m * K + j], u, y[i][m]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int nb = k + 1, nc = arr_c(k), nd = arr_d(k);
+            double Lv[K], Rv[K], sL, sR;
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                Lv[i] = y[0][i] * y[nb][i];
+                Rv[i] = y[nc][i] * y[nd][i];
+            }
+            rescale<K>(Lv, s[0], s[nb], sL);
+            rescale<K>(Rv, s[nc], s[nd], sR);
+#pragma unroll
+            for (int i = 0; i < K; ++i) Lv[i] = pi[i] * Lv[i];
+            // c_j = [V^T (pi o L)]_j [V^-1 R]_j, summed against the central exponentials as it
+            // is formed
+            const double *g = eg + (size_t)3 * k * C * K + (size_t)c * K;
+            double f = 0.0, f1 = 0.0, f2 = 0.0;
+#pragma unroll kEigUnroll
+            for (int j = 0; j < K; ++j) {
+                double A = 0.0, B = 0.0;
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+                    A = fma(Lv[i], ev[i * K + j], A);
+                    B = fma(iv[j * K + i], Rv[i], B);
+                }
+                const double cj = A * B;
+                f = fma(cj, g[j], f);
+                f1 = fma(cj, g[(size_t)C * K + j], f1);
+                f2 = fma(cj, g[(size_t)2 * C * K + j], f2);
+            }
+            double *o = vals + (size_t)4 * k * C * kLanes + (size_t)c * kLanes + l;
+            o[0] = f;
+            o[(size_t)C * kLanes] = f1;
+            o[(size_t)2 * C * kLanes] = f2;
+            o[(size_t)3 * C * kLanes] = sL + sR;
+        }
+    }
+    __syncthreads();
+    // wave k mixes the categories of arrangement k: k_edge's EDGE_DERIV mix, value for value
+    for (int k = w; k < 3; k += nw) {
+        const double *vk = vals + (size_t)4 * k * C * kLanes + l;
+        double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+        if (site < a.S) {
+            const double pw = a.pattern_w[site];
+            double smax = -INFINITY;
+            for (int c = 0; c < C; ++c)
+                if (vk[c * kLanes] > 0.0) smax = fmax(smax, vk[(3 * C + c) * kLanes]);
+            double Ls = 0.0, N1 = 0.0, N2 = 0.0;
+            for (int c = 0; c < C; ++c) {
+                if (!(vk[c * kLanes] > 0.0)) continue;
+                const double sc = vk[(3 * C + c) * kLanes];
+                const double we = a.weights[c] * (sc == smax ? 1.0 : exp(sc - smax));
+                Ls += we * vk[c * kLanes];
+                N1 += we * vk[(C + c) * kLanes];
+                N2 += we * vk[(2 * C + c) * kLanes];
+            }
+            if (Ls > 0.0) {
+                const double d1 = N1 / Ls;
+                v0 = pw * (smax + log(Ls));
+                v1 = pw * d1;
+                v2 = pw * (N2 / Ls - d1 * d1);
+            } else if (pw != 0.0) {
+                v0 = -INFINITY;  // every category has f <= 0 (lnl_node's -inf)
+            }
+        }
+        v0 = wave_sum(v0);
+        v1 = wave_sum(v1);
+        v2 = wave_sum(v2);
+        if (l == 0) {
+            double *p = q.part + 9 * (size_t)blockIdx.x + 3 * k;
+            p[0] = v0;
+            p[1] = v1;
+            p[2] = v2;
+        }
+    }
+}
+
+// second launch: the 9 sums over the workgroups' partials in a fixed order (k_edge_sum's:
+// partial b by thread b % 256, a 64-lane tree, the four waves in order)
+__global__ void __launch_bounds__(256) k_quartet_sum(const double *__restrict__ part, int n,
+                                                     double *__restrict__ result) {
+    __shared__ double red[9 * 4];
+    double s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0.0;
+    for (int b = threadIdx.x; b < n; b += blockDim.x)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] += part[9 * (size_t)b + k];
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        s[k] = wave_sum(s[k]);
+        if ((threadIdx.x & 63) == 0) red[9 * w + k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+        double r = 0.0;
+        for (int k = 0; k < 4; ++k) r += red[9 * k + threadIdx.x];
+        result[threadIdx.x] = r;
+    }
+}
+
+size_t quartet_lds_bytes(int K, int C) { return QuartetLds(K, C).total * sizeof(double); }
+
+// the largest C whose tables and mix area fit the LDS of a CU (K = 2: 25, 4: 24, 20: 19)
+int quartet_max_cat(int K) {
+    int C = 0;
+    while (quartet_lds_bytes(K, C + 1) <= kLdsBytes) ++C;
+    return C;
+}
+
+int node_is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
+
+// what every quartet call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
+int quartet_ready(pu_ctx *c) {
+    int rc = edge_prepare(c);
+    if (rc) return rc;
+    if (c->flags & PU_LNL_ONLY)
+        return set_err(&c->err, PU_E_STATE, "quartet scoring needs PU_KEEP_PARTIALS "
+                       "(PU_LNL_ONLY reuses CLV storage)");
+    if (c->host_p)
+        return set_err(&c->err, PU_E_STATE, "quartet scoring needs an eigen-decomposed model "
+                       "(pu_set_model); this context is on host transition matrices");
+    if (c->asc_mode)
+        return set_err(&c->err, PU_E_STATE, "quartet scoring with the ascertainment-bias "
+                       "correction is not implemented");
+    if (c->K != 2 && c->K != 4 && c->K != 20)
+        return set_err(&c->err, PU_E_ARG, "quartet scoring: K=%d is not supported", c->K);
+    if (c->C > quartet_max_cat(c->K))
+        return set_err(&c->err, PU_E_ARG, "quartet scoring: C=%d categories of K=%d states "
+                       "exceed the LDS of one workgroup (at most %d)", c->C, c->K,
+                       quartet_max_cat(c->K));
+    if (c->q_tiles < c->n_tiles) {
+        dfree(c->d_q_part);
+        c->q_tiles = 0;
+        if ((rc = dalloc(&c->err, &c->d_q_part, 9 * (size_t)c->n_tiles))) return rc;
+        c->q_tiles = c->n_tiles;
+    }
+    if (!c->h_q_res) {
+        HIPCHK(&c->err, hipHostMalloc((void **)&c->h_q_res, 9 * sizeof(double),
+                                      hipHostMallocMapped));
+        HIPCHK(&c->err, hipHostGetDevicePointer((void **)&c->d_q_res_host, c->h_q_res, 0));
+    }
+    return PU_OK;
+}
+
+template <int K>
+void launch_quartet_k(hipStream_t st, const EdgeArgs &a, const QuartetArgs &q) {
+    const dim3 grid((unsigned)a.n_tiles), block(64 * quartet_waves(K, a.C));
+    hipLaunchKernelGGL(k_quartet<K>, grid, block, quartet_lds_bytes(K, a.C), st, a, q);
+}
+
+// one evaluation: out9[3][3] of the three arrangements of x[4] at central lengths t[3]
+int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, double *out9) {
+    EdgeArgs a;
+    edge_fill_args(c, a);
+    QuartetArgs q;
+    for (int i = 0; i < 4; ++i) {
+        q.x[i] = x[i];
+        q.l[i] = l[i];
+    }
+    for (int k = 0; k < 3; ++k) q.t[k] = t[k];
+    q.part = c->d_q_part;
+    const bool prof = c->profile;
+    if (prof) {
+        for (hipEvent_t &e : c->q_ev)
+            if (!e) HIPCHK(&c->err, hipEventCreate(&e));
+        HIPCHK(&c->err, hipEventRecord(c->q_ev[0], c->stream));
+    }
+    switch (c->K) {
+        case 2: launch_quartet_k<2>(c->stream, a, q); break;
+        case 4: launch_quartet_k<4>(c->stream, a, q); break;
+        default: launch_quartet_k<20>(c->stream, a, q); break;
+    }
+    HIPCHK(&c->err, hipGetLastError());
+    if (prof) HIPCHK(&c->err, hipEventRecord(c->q_ev[1], c->stream));
+    hipLaunchKernelGGL(k_quartet_sum, dim3(1), dim3(256), 0, c->stream, c->d_q_part, c->n_tiles,
+                       c->d_q_res_host);
+    HIPCHK(&c->err, hipGetLastError());
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if (prof) HIPCHK(&c->err, hipEventElapsedTime(&c->q_ms, c->q_ev[0], c->q_ev[1]));
+    for (int k = 0; k < 9; ++k) out9[k] = c->h_q_res[k];
+    return PU_OK;
+}
+
+// pu_edge.cpp's newton() as a state machine, so that three of them advance on one launch per
+// step: the same steps, safeguards (a step that lowers the lnL is halved, up to 30 times; a
+// non-concave point moves by expansion or halving), bounds and stopping rule
+struct Newton {
+    double t, r[3], tn;
+    int it = 0, h = 0, evals = 0;
+    bool started = false, done = false;
+
+    double start(double t0) {
+        t = tn = std::min(std::max(t0, kMinLen), kMaxLen);
+        return tn;
+    }
+    void plan(int max_iter) {
+        if (it >= max_iter || !std::isfinite(r[0])) {
+            done = true;
+            return;
+        }
+        const double step = r[2] < 0.0 ? -r[1] / r[2] : (r[1] > 0.0 ? t + 0.1 : -0.5 * t);
+        tn = std::min(std::max(t + step, kMinLen), kMaxLen);
+        h = 0;
+        if (tn == t) done = true;
+    }
+    // the evaluation at tn has arrived
+    void step(const double *rn, double tol, int max_iter) {
+        ++evals;
+        if (!started) {
+            started = true;
+            for (int k = 0; k < 3; ++k) r[k] = rn[k];
+            plan(max_iter);
+        } else if (rn[0] >= r[0] - 1e-13 * fabs(r[0])) {
+            const double dt = fabs(tn - t);
+            t = tn;
+            for (int k = 0; k < 3; ++k) r[k] = rn[k];
+            ++it;
+            if (dt <= tol * (1.0 + t))
+                done = true;
+            else
+                plan(max_iter);
+        } else if (++h >= 30) {
+            done = true;  // no ascent along this direction: t is (numerically) optimal
+        } else {
+            tn = 0.5 * (t + tn);
+        }
+        if (done) tn = t;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int pu_quartet_max_cat(int n_states) {
+    if (n_states != 2 && n_states != 4 && n_states != 20)
+        return set_err(nullptr, PU_E_ARG, "pu_quartet_max_cat: K=%d is not supported", n_states);
+    return quartet_max_cat(n_states);
+}
+
+int pu_quartet_derivs(pu_ctx *c, const int32_t *nodes, const double *lens, const double *t,
+                      double *out9) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!nodes || !lens || !out9) return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: null buffer");
+    int rc = quartet_ready(c);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    NodeSrc x[4];
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < i; ++j)
+            if (nodes[i] == nodes[j])
+                return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: node %d repeated", nodes[i]);
+        if ((rc = edge_node_src(c, nodes[i], &x[i]))) return rc;
+    }
+    for (int i = 0; i < 5; ++i)
+        if (!(lens[i] > 0.0) || !std::isfinite(lens[i]))
+            return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: length %d = %g", i, lens[i]);
+    double tt[3] = {lens[4], lens[4], lens[4]};
+    if (t)
+        for (int k = 0; k < 3; ++k) {
+            if (!(t[k] > 0.0) || !std::isfinite(t[k]))
+                return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: central length %d = %g", k,
+                               t[k]);
+            tt[k] = t[k];
+        }
+    return quartet_eval(c, x, lens, tt, out9);
+}
+
+int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max_iter,
+                 double *scores_out, int32_t *quartets_out, int *n_scored_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (n_rows < 1 || !rows || !scores_out || !quartets_out || !n_scored_out)
+        return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: no rows or a null buffer");
+    if (!(tol > 0.0) || max_iter < 0)
+        return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: tol %g, max_iter %d", tol, max_iter);
+    int rc = quartet_ready(c);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    // the children of every internal node, in the caller's order (pu_set_schedule's ops)
+    std::vector<int> child(2 * (size_t)c->n_nodes, -1);
+    for (int o = 0; o < c->n_ops; ++o) {
+        child[2 * (size_t)c->ops_in[3 * o]] = c->ops_in[3 * o + 1];
+        child[2 * (size_t)c->ops_in[3 * o] + 1] = c->ops_in[3 * o + 2];
+    }
+    const int cap = c->n_tips - 3;
+    int n_scored = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const int32_t *row = rows + 5 * (size_t)r;
+        if (row[0] >= 0) {  // re-orient or restore, as pu_optimise_sweep applies them
+            int k1, k2;
+            if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
+                return rc;
+            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
+            if ((rc = edge_update_ops(c, 1, row, bl))) return rc;
+        }
+        if (row[3] < 0) continue;
+        const int nod = row[3], par = row[4];
+        int kc;
+        if ((rc = edge_key(c, nod, par, &kc))) return rc;
+        if (node_is_tip(c, nod) || node_is_tip(c, par)) continue;
+        // the quartet (children of NOD | SIB, GPA); on the root edge both are PAR's children
+        const int nodes[4] = {child[2 * (size_t)nod], child[2 * (size_t)nod + 1],
+                              row[0] >= 0 ? row[1] : child[2 * (size_t)par],
+                              row[0] >= 0 ? row[2] : child[2 * (size_t)par + 1]};
+        if (n_scored >= cap)
+            return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: more than n_tips - 3 = %d internal "
+                           "edges in the rows", cap);
+        NodeSrc x[4];
+        double l[4];
+        for (int i = 0; i < 4; ++i) {
+            int key;
+            if (nodes[i] < 0)
+                return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: node %d has no children in the "
+                               "schedule", i < 2 ? nod : par);
+            if ((rc = edge_node_src(c, nodes[i], &x[i])) ||
+                (rc = edge_key(c, nodes[i], i < 2 ? nod : par, &key)))
+                return rc;
+            l[i] = c->up_len[key];
+        }
+        Newton nt[3];
+        double t[3], out9[9];
+        for (int k = 0; k < 3; ++k) t[k] = nt[k].start(c->up_len[kc]);
+        while (!(nt[0].done && nt[1].done && nt[2].done)) {
+            if ((rc = quartet_eval(c, x, l, t, out9))) return rc;
+            for (int k = 0; k < 3; ++k) {
+                if (!nt[k].done) nt[k].step(out9 + 3 * k, tol, max_iter);
+                t[k] = nt[k].tn;
+            }
+        }
+        for (int k = 0; k < 3; ++k) {
+            double *s = scores_out + 12 * (size_t)n_scored + 4 * k;
+            s[0] = nt[k].t;
+            s[1] = nt[k].r[0];
+            s[2] = nt[k].r[1];
+            s[3] = (double)nt[k].evals;
+        }
+        int32_t *qo = quartets_out + 6 * (size_t)n_scored;
+        qo[0] = nod;
+        qo[1] = par;
+        for (int i = 0; i < 4; ++i) qo[2 + i] = nodes[i];
+        ++n_scored;
+    }
+    *n_scored_out = n_scored;
+    // every node is back in its post-order orientation by the restore rows' updates; one
+    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
+    double lnl;
+    return pu_run(c, &lnl, nullptr);
+}
+
+int pu_quartet_kernel_ms(pu_ctx *c, double *ms_out) {
+    if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
+    *ms_out = (double)c->q_ms;
+    return PU_OK;
+}
+
+}  // extern "C"

@@ -31,7 +31,10 @@ neighbour-joining (or BIONJ) tree of those distances (``phylo_utils_amd.nj``; th
 no tree builder), written as Newick to ``-o`` when given, and the ``lnL = `` line is that tree's,
 after ``--optimise`` when asked; with ``--bootstrap R`` (and the seed of ``--seed``) the Newick
 carries, as internal node labels, the support in percent of every split over R bootstrap
-replicates (``phylo_utils_amd.bootstrap``).
+replicates (``phylo_utils_amd.bootstrap``);
+``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
+interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
+rounds, default 50); ``-o`` then receives the final Newick.
 """
 from __future__ import annotations
 
@@ -155,13 +158,22 @@ def parse_cli(argv=None):
     ap.add_argument("--bootstrap", type=int, default=None, metavar="R",
                     help="with --nj: label the tree's splits with their support in percent "
                          "over R bootstrap replicates (seed: --seed)")
+    ap.add_argument("--nni", type=int, nargs="?", const=50, default=None, metavar="ROUNDS",
+                    help="after -t or --nj: nearest-neighbour-interchange search (at most ROUNDS "
+                         "rounds, default 50) before the lnL line; -o receives the final Newick")
     ap.add_argument("-o", "--output", type=str, default=None,
-                    help="output file of --simulate / --distances (default: stdout) / --nj")
+                    help="output file of --simulate / --distances (default: stdout) / --nj / "
+                         "--nni")
     return ap.parse_args(argv)
 
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "nni", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--nni excludes --simulate and --distances")
+        if args.nni < 0:
+            raise ValueError("--nni needs a non-negative number of rounds")
     if getattr(args, "bootstrap", None) is not None:
         if getattr(args, "nj", None) is None:
             raise ValueError("--bootstrap needs --nj")
@@ -228,6 +240,12 @@ def run(args, out=None):
     tm.initialise()
     if args.optimise:
         tm.optimise_branch_lengths(sweeps=args.optimise, method=args.optimiser)
+    if getattr(args, "nni", None) is not None:
+        tree, _, _ = tm.nni_search(max_rounds=args.nni, sweeps=max(args.optimise, 1),
+                                   method=args.optimiser)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
     lnl = tm.compute_likelihood_at_edge(*tm.traversal.root_edge).sum()
     out.write("lnL = {}\n".format(lnl))
     return lnl

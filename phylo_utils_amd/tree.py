@@ -324,3 +324,98 @@ class Traversal(object):
 
     def root_length(self):
         return float(self.brlens[self.root_edge])
+
+
+# ---------------------------------------------------------------- nearest-neighbour interchange
+# Host helpers of the NNI search (phylo_utils_amd.nni).  Nodes are named by their
+# Traversal index on prepare_tree(tree), an internal edge by (NOD, PAR) as the optimising
+# traversal's rows name it: NOD the child end, PAR its parent -- the root edge by (LEFT, RIGHT).
+# The quartet around the edge is (x0, x1 | x2, x3): NOD's two children, then NOD's sibling and
+# grandparent side (on the root edge: RIGHT's two children).  Arrangement 1 is (x0, x2 | x1, x3),
+# arrangement 2 is (x0, x3 | x1, x2).
+
+def internal_edges(tree):
+    """The internal edges [(NOD, PAR)] of `tree`, in optimising-traversal order: the rows whose
+    two ends both have children (the edges pu_nni_sweep scores; N - 3 of them)."""
+    tr = Traversal(prepare_tree(tree))
+    internal = set(int(p) for p in tr.postorder_traversal[:, 0])
+    return [(int(r[3]), int(r[4])) for r in tr.optimising_traversal
+            if r[3] >= 0 and int(r[3]) in internal and int(r[4]) in internal]
+
+
+def apply_nni_moves(tree, moves):
+    """prepare_tree(tree) with every move (nod, par, which, length) applied: `which` 1 exchanges
+    x1 with x2, 2 exchanges x0 with x2 (the module comment above), every subtree keeping its own
+    edge length; `length`, when not None, replaces the central edge's.  The moves' edges must not
+    share an end node (all are taken on the node numbering of the tree as given)."""
+    t = prepare_tree(tree)
+    tr = Traversal(t)
+    node = {i: n for n, i in tr.node_dict.items()}
+    left, right = t.seed_node.children
+    ends = set()
+    for nod, par, which, length in moves:
+        if which not in (1, 2):
+            raise ValueError("which must be 1 or 2, got %r" % (which,))
+        if nod not in node or par not in node:
+            raise ValueError("no node %r or %r in the tree" % (nod, par))
+        if nod in ends or par in ends:
+            raise ValueError("moves share node %d or %d" % (nod, par))
+        ends.update((nod, par))
+        n, p = node[nod], node[par]
+        if n.is_leaf() or p.is_leaf():
+            raise ValueError("edge (%d, %d) is not internal" % (nod, par))
+        root_edge = (n is left and p is right) or (n is right and p is left)
+        if root_edge:
+            x2 = p.children[0]
+        elif n.parent is p:
+            x2 = next(c for c in p.children if c is not n)
+        else:
+            raise ValueError("(%d, %d): no edge with child end %d" % (nod, par, nod))
+        mine = n.children[2 - which]
+        i, j = n.children.index(mine), p.children.index(x2)
+        n.children[i], p.children[j] = x2, mine
+        x2.parent, mine.parent = n, p
+        n.label = None  # a support label belonged to the split that is gone
+        if root_edge:
+            p.label = None
+        if length is not None:
+            if root_edge:  # the root edge's length is the larger of its two halves
+                left.length, right.length = float(length), 0.0
+            else:
+                n.length = float(length)
+    return t
+
+
+def apply_nni(tree, nod, par, which, length=None):
+    """A new Tree: the nearest-neighbour interchange `which` (1 or 2) at internal edge
+    (nod, par) of `tree`; every length is kept, the central one replaced by `length` if given."""
+    return apply_nni_moves(tree, [(nod, par, which, length)])
+
+
+def select_moves(candidates):
+    """The round's moves from candidates [dict(nod, par, which, gain, ...)]: by descending gain,
+    ties by the sorted (nod, par) pair, taken greedily, skipping every candidate whose edge shares
+    an end node with an edge already taken."""
+    order = sorted(candidates, key=lambda m: (-m["gain"], tuple(sorted((m["nod"], m["par"])))))
+    taken, used = [], set()
+    for m in order:
+        if m["nod"] in used or m["par"] in used:
+            continue
+        taken.append(m)
+        used.update((m["nod"], m["par"]))
+    return taken
+
+
+def with_lengths(tree, brlens):
+    """A copy of the prepared `tree` whose edge lengths are `brlens` (Traversal.brlens, keyed by
+    node-index pairs); the root edge's length goes to the seed's first child."""
+    t = tree.copy()
+    tr = Traversal(t)
+    bl = BranchLengths(brlens)
+    left, right = t.seed_node.children
+    for n, i in tr.node_dict.items():
+        if n.parent is t.seed_node:
+            n.length = float(bl[tr.root_edge]) if n is left else 0.0
+        else:
+            n.length = float(bl[(i, tr.node_dict[n.parent])])
+    return t

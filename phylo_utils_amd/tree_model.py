@@ -581,6 +581,26 @@ class TreeModel(object):
         self._pull_lengths()
         return self._lnl
 
+    # ------------------------------------------------------------------ tree search
+    def quartet_derivatives(self, nodes, lens, t=None):
+        """(lnL, dlnL/dt, d2lnL/dt2) [3][3] of the three arrangements of four nodes on their
+        current partials (``nni.quartet_derivatives``, pu_quartet_derivs)."""
+        from . import nni
+        return nni.quartet_derivatives(self, nodes, lens, t)
+
+    def nni_scores(self, tol=1e-8, max_iter=50):
+        """Every internal edge's three arrangements, central lengths optimised, in one pass of
+        the optimising traversal (``nni.nni_scores``, pu_nni_sweep): (quartets [n][6], scores
+        [n][3][4])."""
+        from . import nni
+        return nni.nni_scores(self, tol, max_iter)
+
+    def nni_search(self, max_rounds=50, min_gain=1e-3, sweeps=1, tol=1e-8, method="newton"):
+        """Nearest-neighbour-interchange search from the current tree (``nni.nni_search``):
+        returns (tree, lnL, history); the model ends on that tree with its lengths optimised."""
+        from . import nni
+        return nni.nni_search(self, max_rounds, min_gain, sweeps, tol, method)
+
     # ------------------------------------------------------------------ simulation
     def simulate(self, n_sites, seed=0, first_site=0, return_categories=False,
                  return_ancestral=False, return_cum=False):
