@@ -1,8 +1,8 @@
 // pu_ctx.h -- the device context behind the C ABI and the helpers every C-ABI translation
-// unit shares (pu_capi.cpp: contexts, planner, traversal; pu_edge.cpp: edge likelihoods,
-// derivatives and branch-length optimisation).  The host layer of the stateless calls (device
-// buffers, per-device state, host-call scope, pair-call argument rules) is pu_service.h.  Not
-// part of the public ABI.
+// unit shares (pu_capi.cpp: contexts, traversal; pu_edge.cpp: edge likelihoods, derivatives and
+// branch-length optimisation).  The traversal planner is host-only and does not see a context
+// (pu_plan.h).  The host layer of the stateless calls (device buffers, per-device state,
+// host-call scope, pair-call argument rules) is pu_service.h.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -243,6 +243,8 @@ struct pu_ctx {
 namespace pu {
 // tiles per layout row of a context's tiled CLV / scaler / root buffers
 inline int64_t ctx_pitch(const pu_ctx *c) { return tile_pitch(c->S) + c->pitch_extra; }
+// sites per (slot, category) layout row as allocated: the largest pitch the context may pick
+inline size_t padS(const pu_ctx *c) { return (size_t)(tile_pitch(c->S) + c->pitch_pad) * kTile; }
 // shared by the C-ABI translation units (pu_capi.cpp)
 int check_ready(pu_ctx *c);
 // one traversal launch of a context, prepared (pu_enqueue, pu_batch_enqueue): checks, provider

@@ -1,12 +1,12 @@
-// pu_internal.h -- shared between the HIP kernels (pu_kernels.hip) and the
-// C-ABI / planning layer (pu_capi.cpp).  Not part of the public ABI.
+// pu_internal.h -- shared between the HIP kernels (pu_kernels.hip), the host-only
+// planner (pu_plan.cpp) and the C-ABI layer (pu_capi.cpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace pu {
 
-// How an op finds its children (pu_capi.cpp canonicalises the child order):
+// How an op finds its children (pu_plan.cpp canonicalises the child order):
 //   PAT_LC  a: a waiting parent in LDS stash slot ia,   b: the previous op's parent
 //   PAT_MC  a: a waiting parent read back from HBM,      b: the previous op's parent
 //   PAT_CT  a: the previous op's parent,                 b: a tip
@@ -26,7 +26,7 @@ struct OpDesc {
     int ib;        // child b: HBM slot (PAT_MM) or tip slot (PAT_CT, PAT_TT, PAT_MT)
     int dst;       // LDS stash slot the parent waits in for its consumer, -1: none
     int use0;      // the op's first tip use, counted from its staging chunk's first use
-                   // (filled by upload_schedule; the DNA kernel indexes the staged codes
+                   // (filled by plan_schedule; the DNA kernel indexes the staged codes
                    // with it instead of keeping a running count)
     long long par_off;  // the parent's CLV slot as a byte offset, (par_slot & ~kReadBack) x
                         // slot bytes (0: not stored); its scaler slot is par_off / K.  K = 20:
