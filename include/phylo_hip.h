@@ -263,6 +263,41 @@ int pu_nni_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int m
                  double *scores_out, int32_t *quartets_out, int *n_scored_out);
 /* HIP-event time (ms) of the last k_quartet launch made while pu_ctx_profile was on. */
 int pu_quartet_kernel_ms(pu_ctx *ctx, double *ms_out);
+/* ---- marginal ancestral states and site-rate posteriors -------------------- */
+/* The largest category count the ancestral kernel takes for n_states = 2, 4 or 20: its LDS use
+ * of one workgroup against the 160 KiB of a CU, and no more than a context holds (64, 50, 10);
+ * PU_E_ARG for other n_states.  Host only. */
+int pu_ancestral_max_cat(int n_states);
+/* The marginal posterior of `node`'s state at every pattern, from the current partials of
+ * `node` (the subtree on its side of the edge) and of `other` (everything else), the two ends
+ * of one edge, at `length` (< 0: the edge's current length), like pu_edge_lnl on the nodes'
+ * CURRENT partials: map_state[S] the most probable state (the lowest index on a tie),
+ * map_prob[S] its posterior, post[S][K] all posteriors (NULL: not wanted), *lnl_out the
+ * pattern-weighted lnL.  Changes nothing in the context.  PU_KEEP_PARTIALS contexts on the
+ * device eigen-system (a reversible model) without an ascertainment correction (else
+ * PU_E_STATE); PU_E_ARG: a null buffer, a node out of range, nodes not joined by an edge, a tip
+ * as `node`, a zero or non-finite length, more categories than pu_ancestral_max_cat. */
+int pu_ancestral_edge(pu_ctx *ctx, int node, int other, double length, uint8_t *map_state,
+                      double *map_prob, double *post, double *lnl_out);
+/* Every internal node in one pass over the optimising traversal (rows as pu_optimise_sweep
+ * takes them, lengths the context's current ones).  Every re-orientation / restore row is
+ * applied.  Row 0 reconstructs each end of the root edge from the other, every later row
+ * (PAR, SIB, GPA, NOD, PAR) reconstructs NOD from PAR -- internal nodes only, each once, in that
+ * order: nodes_out[n], map_state_out[n][S], map_prob_out[n][S], post_out[n][S][K] (NULL: not
+ * wanted), node_lnl_out[n] (every entry the tree's lnL, by the pulley principle), *n_nodes_out
+ * = n <= n_tips - 2; the buffers hold n_tips - 2 entries, more internal nodes in the rows are
+ * PU_E_ARG.  The results stay on the device during the pass and are copied once per array.
+ * The pass ends with a full traversal, so the context's partials, lnL and sitewise lnL are
+ * bitwise those of pu_run before the call.  Refusals as pu_ancestral_edge. */
+int pu_ancestral_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *nodes_out,
+                       uint8_t *map_state_out, double *map_prob_out, double *post_out,
+                       double *node_lnl_out, int *n_nodes_out);
+/* Posterior of the rate category of every pattern, cat_post_out[S][C] (NULL: not wanted), and
+ * its mean rate sum_c r(c) rate_c, mean_rate_out[S]: one launch on the root edge, on the
+ * partials a traversal leaves.  Refusals as pu_ancestral_edge. */
+int pu_site_rates(pu_ctx *ctx, double *cat_post_out, double *mean_rate_out);
+/* HIP-event time (ms) of the last k_ancestral launch made while pu_ctx_profile was on. */
+int pu_ancestral_kernel_ms(pu_ctx *ctx, double *ms_out);
 /* Current lengths in pu_set_schedule's layout: brlens_out[n_ops][2], root length. */
 int pu_get_branch_lengths(pu_ctx *ctx, double *brlens_out, double *root_len_out);
 

@@ -90,6 +90,11 @@ SIGNATURES = {
     "pu_quartet_derivs": (_c_int, [_P, _P, _P, _P, _P]),
     "pu_nni_sweep": (_c_int, [_P, _c_int, _P, _c_dbl, _c_int, _P, _P, _P]),
     "pu_quartet_kernel_ms": (_c_int, [_P, _P]),
+    "pu_ancestral_max_cat": (_c_int, [_c_int]),
+    "pu_ancestral_edge": (_c_int, [_P, _c_int, _c_int, _c_dbl, _P, _P, _P, _P]),
+    "pu_ancestral_sweep": (_c_int, [_P, _c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pu_site_rates": (_c_int, [_P, _P, _P]),
+    "pu_ancestral_kernel_ms": (_c_int, [_P, _P]),
     "pu_get_branch_lengths": (_c_int, [_P, _P, _P]),
     "pu_lnl_branch": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pu_lnl_branch_derivs": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _P, _P, _P, _P, _P, _P,

@@ -1,0 +1,466 @@
+// pu_ancestral.hip -- marginal ancestral states and site-rate posteriors on the device-resident
+// CLVs of a context: the gfx950 kernel that turns the two partials at the ends of
+// an edge into the posterior of one end's state, and its C ABI (include/phylo_hip.h):
+//   pu_ancestral_max_cat   the kernel's category limit per alphabet (host only)
+//   pu_ancestral_edge      the posterior of one node's state from the far end of one edge
+//   pu_ancestral_sweep     one pass of the optimising traversal that reconstructs every
+//                          internal node
+//   pu_site_rates          posterior of the rate category and mean rate of every pattern
+//
+// While the optimising traversal stands on edge (n, o), partials[n] holds the subtree below n
+// and partials[o], re-oriented, everything else.  For a reversible model, with A, B the two
+// vectors of (site, category c), sA, sB their log scalers and t the edge length:
+//   g_c(i)  = pi_i A_c(i) sum_j P_c(t)[i][j] B_c(j)      joint of state i at n and the data
+//   F_c     = sum_i g_c(i),  sigma_c = sA_c + sB_c,  m = max_c sigma_c
+//   Z       = sum_c w_c e^{sigma_c - m} F_c
+//   q(i)    = sum_c w_c e^{sigma_c - m} g_c(i) / Z       posterior of state i at n
+//   r(c)    = w_c e^{sigma_c - m} F_c / Z                posterior of category c
+//   lnL_s   = m + log Z                                  the site's log-likelihood
+// The kernel only reads the context: no pre-order pass, no second set of partials.
+//
+// Mapping (k_edge's): a workgroup is one 64-site tile, a lane a site, wave w owns
+// rate categories w, w + nw, ...; the categories of a site meet in LDS, where wave 0 mixes them.
+// P_c(t) is built once per workgroup into LDS from the eigen-system with build_p's arithmetic.
+// Every sum runs in a fixed order (categories ascending, states ascending); every workgroup
+// writes its weighted lnL sum and a one-workgroup second launch adds them in k_edge_sum's order.
+#include <math.h>
+
+#include <cmath>
+
+#include "pu_ctx.h"
+#include "pu_edge_dev.h"
+
+using namespace pu;
+
+namespace {
+
+struct AncArgs {
+    NodeSrc n, o;        // the node reconstructed, the other end of the edge
+    double t;            // the edge length
+    uint8_t *map_state;  // [S] argmax_i q(i), lowest index on a tie (nullptr: not written)
+    double *map_prob;    // [S] its posterior (nullptr: not written)
+    double *post;        // [S][K] q (nullptr: not written)
+    double *cat_post;    // [S][C] r (nullptr: not written)
+    double *mean_rate;   // [S] sum_c r(c) rate_c (nullptr: not written)
+    double *part;        // [grid] per-workgroup sums of pattern weight x lnL_s
+};
+
+constexpr int kAncMaxWaves = 8;
+__host__ __device__ inline int anc_waves(int C) { return C < kAncMaxWaves ? C : kAncMaxWaves; }
+
+// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][exponentials
+// C*K][P C*K*K][per (category, site): g(0..K-1), F, sigma -- later the mix weight: C*(K+2)*64]
+struct AncLds {
+    size_t evecs, ivecs, evals, pi, rates, ex, P, vals, total;
+    __host__ __device__ AncLds(int K, int C) {
+        evecs = 0;
+        ivecs = evecs + (size_t)K * K;
+        evals = ivecs + (size_t)K * K;
+        pi = evals + K;
+        rates = pi + K;
+        ex = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+        P = ex + (size_t)C * K;
+        vals = P + (size_t)C * K * K;
+        total = vals + (size_t)C * (K + 2) * kLanes;
+    }
+};
+constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
+constexpr int kCtxMaxCat = 64;            // pu_ctx_create takes no more categories
+
+template <int K>
+__global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, AncArgs q) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int C = a.C;
+    const AncLds L(K, C);
+    const int tile = blockIdx.x, l = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int64_t site = (int64_t)tile * kLanes + l;
+    const int64_t site_c = site < a.S ? site : a.S - 1;
+    const double *ev = lds + L.evecs, *iv = lds + L.ivecs, *el = lds + L.evals,
+                 *pi = lds + L.pi, *rt = lds + L.rates, *ex = lds + L.ex, *P = lds + L.P;
+    double *vals = lds + L.vals;
+    constexpr int kRow = (K + 2) * kLanes;  // doubles per category in vals
+
+    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
+        lds[L.evecs + i] = a.evecs[i];
+        lds[L.ivecs + i] = a.ivecs[i];
+    }
+    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+        lds[L.evals + i] = a.evals[i];
+        lds[L.pi + i] = a.pi[i];
+    }
+    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    __syncthreads();
+    // P_c(t) = evecs diag(e^{lambda (t r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
+    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
+        const int k = idx % K, c = idx / K;
+        lds[L.ex + idx] = exp(el[k] * (q.t * rt[c]));
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
+        const int ij = idx % (K * K), c = idx / (K * K);
+        const int i = ij / K, j = ij - i * K;
+        const double *e = ex + c * K;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
+        lds[L.P + idx] = acc;
+    }
+    __syncthreads();
+
+    // K = 20: the rows of P are read from LDS where they are used (unrolled, they are hoisted
+    // and spill); y_i waits in the lane's own LDS slot, so the row loop indexes no registers
+    constexpr int kRowUnroll = K > 4 ? 1 : K;
+    for (int c = w; c < C; c += nw) {
+        double A[K], B[K], sA, sB;
+        node_vec<K>(a, q.n, c, tile, l, site_c, A, sA);
+        node_vec<K>(a, q.o, c, tile, l, site_c, B, sB);
+        const double *Pc = P + (size_t)c * K * K;
+        double *g = vals + (size_t)c * kRow + l;
+#pragma unroll kRowUnroll
+        for (int i = 0; i < K; ++i) {
+            double y = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) y = fma(Pc[i * K + j], B[j], y);
+            g[i * kLanes] = y;
+        }
+        double F = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const double gi = (pi[i] * A[i]) * g[i * kLanes];
+            g[i * kLanes] = gi;
+            F += gi;
+        }
+        g[K * kLanes] = F;
+        g[(K + 1) * kLanes] = sA + sB;
+    }
+    __syncthreads();
+    if (w != 0) return;
+
+    // wave 0 mixes the categories of its 64 sites.  Only categories with F_c > 0 take part
+    // (k_edge's rule: an all-zero vector keeps an unrescaled scaler, which must not set m)
+    double v0 = 0.0;
+    if (site < a.S) {
+        double *vs = vals + l;
+        double m = -INFINITY;
+        for (int c = 0; c < C; ++c)
+            if (vs[(size_t)c * kRow + K * kLanes] > 0.0)
+                m = fmax(m, vs[(size_t)c * kRow + (K + 1) * kLanes]);
+        double Z = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double F = vs[(size_t)c * kRow + K * kLanes];
+            double we = 0.0;
+            if (F > 0.0) {
+                const double sc = vs[(size_t)c * kRow + (K + 1) * kLanes];
+                we = a.weights[c] * (sc == m ? 1.0 : exp(sc - m));
+            }
+            vs[(size_t)c * kRow + (K + 1) * kLanes] = we;  // the mix weight replaces sigma_c
+            Z += we * F;
+        }
+        int best = 0;
+        double bestq = 0.0;
+        dbl2 *post = q.post ? reinterpret_cast<dbl2 *>(q.post + (size_t)site * K) : nullptr;
+        constexpr int kPairUnroll = K > 4 ? 1 : K / 2;
+#pragma unroll kPairUnroll
+        for (int ip = 0; ip < K / 2; ++ip) {
+            double q0 = 0.0, q1 = 0.0;
+            for (int c = 0; c < C; ++c) {
+                const double we = vs[(size_t)c * kRow + (K + 1) * kLanes];
+                q0 += we * vs[(size_t)c * kRow + (2 * ip) * kLanes];
+                q1 += we * vs[(size_t)c * kRow + (2 * ip + 1) * kLanes];
+            }
+            q0 = q0 / Z;
+            q1 = q1 / Z;
+            if (ip == 0 || q0 > bestq) {
+                best = 2 * ip;
+                bestq = q0;
+            }
+            if (q1 > bestq) {
+                best = 2 * ip + 1;
+                bestq = q1;
+            }
+            if (post) post[ip] = dbl2{q0, q1};  // [site][state]: K = 4 two 16-byte stores
+        }
+        if (q.map_state) q.map_state[site] = (uint8_t)best;
+        if (q.map_prob) q.map_prob[site] = bestq;
+        if (q.cat_post || q.mean_rate) {
+            double mr = 0.0;
+            for (int c = 0; c < C; ++c) {
+                const double r = vs[(size_t)c * kRow + (K + 1) * kLanes] *
+                                 vs[(size_t)c * kRow + K * kLanes] / Z;
+                if (q.cat_post) q.cat_post[(size_t)site * C + c] = r;
+                mr += r * rt[c];
+            }
+            if (q.mean_rate) q.mean_rate[site] = mr;
+        }
+        const double pw = a.pattern_w[site];
+        if (Z > 0.0)
+            v0 = pw * (m + log(Z));
+        else if (pw != 0.0)
+            v0 = -INFINITY;  // every category has F = 0 (lnl_node's -inf)
+    }
+    v0 = wave_sum(v0);
+    if (l == 0) q.part[blockIdx.x] = v0;
+}
+
+// second launch: the workgroups' sums in a fixed order (k_edge_sum's: partial b by thread
+// b % 256, a 64-lane tree, the four waves in order)
+__global__ void __launch_bounds__(256) k_ancestral_sum(const double *__restrict__ part, int n,
+                                                       double *__restrict__ result) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n; b += blockDim.x) s += part[b];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = 0.0;
+        for (int k = 0; k < 4; ++k) r += red[k];
+        *result = r;
+    }
+}
+
+size_t anc_lds_bytes(int K, int C) { return AncLds(K, C).total * sizeof(double); }
+
+// the largest C whose P matrices and mix area fit the LDS of a CU, and a context can hold
+// (K = 2: 64, 4: 50, 20: 10)
+int anc_max_cat(int K) {
+    int C = 0;
+    while (C < kCtxMaxCat && anc_lds_bytes(K, C + 1) <= kLdsBytes) ++C;
+    return C;
+}
+
+bool is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
+
+// a device buffer owned by one call
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf() { dfree(p); }
+    int alloc(std::string *err, size_t n) { return dalloc(err, &p, n); }
+};
+
+// what every call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
+int ancestral_ready(pu_ctx *c, const char *what) {
+    int rc = edge_prepare(c);
+    if (rc) return rc;
+    if (c->flags & PU_LNL_ONLY)
+        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
+                       "storage)", what);
+    if (c->host_p)
+        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
+                       "(pu_set_model); this context is on host transition matrices", what);
+    if (c->asc_mode)
+        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
+                       "implemented", what);
+    if (c->K != 2 && c->K != 4 && c->K != 20)
+        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
+    if (c->C > anc_max_cat(c->K))
+        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
+                       "one workgroup (at most %d)", what, c->C, c->K, anc_max_cat(c->K));
+    if (c->a_tiles < c->n_tiles) {
+        dfree(c->d_a_part);
+        c->a_tiles = 0;
+        if ((rc = dalloc(&c->err, &c->d_a_part, (size_t)c->n_tiles))) return rc;
+        c->a_tiles = c->n_tiles;
+    }
+    return PU_OK;
+}
+
+template <int K>
+void launch_ancestral_k(hipStream_t st, const EdgeArgs &a, const AncArgs &q) {
+    const dim3 grid((unsigned)a.n_tiles), block(64 * anc_waves(a.C));
+    hipLaunchKernelGGL(k_ancestral<K>, grid, block, anc_lds_bytes(K, a.C), st, a, q);
+}
+
+// one k_ancestral launch and its sum, queued on the context's stream; the weighted lnL sum
+// lands in *lnl_dev (device memory)
+int ancestral_enqueue(pu_ctx *c, AncArgs q, double *lnl_dev) {
+    EdgeArgs a;
+    edge_fill_args(c, a);
+    q.part = c->d_a_part;
+    const bool prof = c->profile;
+    if (prof) {
+        for (hipEvent_t &e : c->a_ev)
+            if (!e) HIPCHK(&c->err, hipEventCreate(&e));
+        HIPCHK(&c->err, hipEventRecord(c->a_ev[0], c->stream));
+    }
+    switch (c->K) {
+        case 2: launch_ancestral_k<2>(c->stream, a, q); break;
+        case 4: launch_ancestral_k<4>(c->stream, a, q); break;
+        default: launch_ancestral_k<20>(c->stream, a, q); break;
+    }
+    HIPCHK(&c->err, hipGetLastError());
+    if (prof) HIPCHK(&c->err, hipEventRecord(c->a_ev[1], c->stream));
+    hipLaunchKernelGGL(k_ancestral_sum, dim3(1), dim3(256), 0, c->stream, c->d_a_part,
+                       c->n_tiles, lnl_dev);
+    HIPCHK(&c->err, hipGetLastError());
+    return PU_OK;
+}
+
+// after the stream has drained: the time of the last launch made while profiling
+int ancestral_stamp(pu_ctx *c) {
+    if (c->profile && c->a_ev[1])
+        HIPCHK(&c->err, hipEventElapsedTime(&c->a_ms, c->a_ev[0], c->a_ev[1]));
+    return PU_OK;
+}
+
+template <class T>
+int to_host(pu_ctx *c, T *dst, const T *src, size_t n) {
+    if (n) HIPCHK(&c->err, hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return PU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pu_ancestral_max_cat(int n_states) {
+    if (n_states != 2 && n_states != 4 && n_states != 20)
+        return set_err(nullptr, PU_E_ARG, "pu_ancestral_max_cat: K=%d is not supported",
+                       n_states);
+    return anc_max_cat(n_states);
+}
+
+int pu_ancestral_edge(pu_ctx *c, int node, int other, double length, uint8_t *map_state,
+                      double *map_prob, double *post, double *lnl_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!map_state || !map_prob || !lnl_out)
+        return set_err(&c->err, PU_E_ARG, "pu_ancestral_edge: null buffer");
+    int rc = ancestral_ready(c, "ancestral reconstruction");
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    int key;
+    AncArgs q = {};
+    if ((rc = edge_key(c, node, other, &key)) || (rc = edge_node_src(c, node, &q.n)) ||
+        (rc = edge_node_src(c, other, &q.o)))
+        return rc;
+    if (is_tip(c, node))
+        return set_err(&c->err, PU_E_ARG, "pu_ancestral_edge: node %d is a tip", node);
+    if (!std::isfinite(length) || length == 0.0)
+        return set_err(&c->err, PU_E_ARG, "pu_ancestral_edge: length %g", length);
+    q.t = length < 0.0 ? c->up_len[key] : length;
+    const size_t S = (size_t)c->S, K = (size_t)c->K;
+    DevBuf<uint8_t> d_state;
+    DevBuf<double> d_prob, d_post, d_lnl;
+    if ((rc = d_state.alloc(&c->err, S)) || (rc = d_prob.alloc(&c->err, S)) ||
+        (rc = d_post.alloc(&c->err, post ? S * K : 0)) || (rc = d_lnl.alloc(&c->err, 1)))
+        return rc;
+    q.map_state = d_state.p;
+    q.map_prob = d_prob.p;
+    q.post = d_post.p;
+    if ((rc = ancestral_enqueue(c, q, d_lnl.p))) return rc;
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if ((rc = ancestral_stamp(c)) || (rc = to_host(c, map_state, d_state.p, S)) ||
+        (rc = to_host(c, map_prob, d_prob.p, S)) ||
+        (rc = to_host(c, post, d_post.p, post ? S * K : 0)) ||
+        (rc = to_host(c, lnl_out, d_lnl.p, 1)))
+        return rc;
+    return PU_OK;
+}
+
+int pu_ancestral_sweep(pu_ctx *c, int n_rows, const int32_t *rows, int32_t *nodes_out,
+                       uint8_t *map_state_out, double *map_prob_out, double *post_out,
+                       double *node_lnl_out, int *n_nodes_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (n_rows < 1 || !rows || !nodes_out || !map_state_out || !map_prob_out || !node_lnl_out ||
+        !n_nodes_out)
+        return set_err(&c->err, PU_E_ARG, "pu_ancestral_sweep: no rows or a null buffer");
+    int rc = ancestral_ready(c, "ancestral reconstruction");
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    const int cap = c->n_tips - 2;
+    const size_t S = (size_t)c->S, K = (size_t)c->K;
+    // the results of all nodes stay on the device until the walk is over
+    DevBuf<uint8_t> d_state;
+    DevBuf<double> d_prob, d_post, d_lnl;
+    if (cap > 0 &&
+        ((rc = d_state.alloc(&c->err, cap * S)) || (rc = d_prob.alloc(&c->err, cap * S)) ||
+         (rc = d_post.alloc(&c->err, post_out ? cap * S * K : 0)) ||
+         (rc = d_lnl.alloc(&c->err, (size_t)cap))))
+        return rc;
+    int count = 0;
+    // reconstruct `node` from `other`, the far end of their edge, on the current partials
+    auto visit = [&](int node, int other, int key) -> int {
+        if (is_tip(c, node)) return PU_OK;
+        if (count >= cap)
+            return set_err(&c->err, PU_E_ARG, "pu_ancestral_sweep: more than n_tips - 2 = %d "
+                           "internal nodes in the rows", cap);
+        AncArgs q = {};
+        int r;
+        if ((r = edge_node_src(c, node, &q.n)) || (r = edge_node_src(c, other, &q.o))) return r;
+        q.t = c->up_len[key];
+        q.map_state = d_state.p + count * S;
+        q.map_prob = d_prob.p + count * S;
+        q.post = post_out ? d_post.p + count * S * K : nullptr;
+        if ((r = ancestral_enqueue(c, q, d_lnl.p + count))) return r;
+        nodes_out[count++] = node;
+        return PU_OK;
+    };
+    for (int r = 0; r < n_rows; ++r) {
+        const int32_t *row = rows + 5 * (size_t)r;
+        if (row[0] >= 0) {  // re-orient or restore, as pu_optimise_sweep applies them
+            int k1, k2;
+            if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
+                return rc;
+            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
+            if ((rc = edge_update_ops(c, 1, row, bl))) return rc;
+        }
+        if (row[3] < 0) continue;
+        const int nod = row[3], par = row[4];
+        int key;
+        if ((rc = edge_key(c, nod, par, &key))) return rc;
+        // NOD from PAR, which holds everything but NOD's subtree; on the root edge (row 0) each
+        // end is the other's complement
+        if ((rc = visit(nod, par, key))) return rc;
+        if (r == 0 && (rc = visit(par, nod, key))) return rc;
+    }
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)count;
+    if ((rc = ancestral_stamp(c)) || (rc = to_host(c, map_state_out, d_state.p, n * S)) ||
+        (rc = to_host(c, map_prob_out, d_prob.p, n * S)) ||
+        (rc = to_host(c, post_out, d_post.p, post_out ? n * S * K : 0)) ||
+        (rc = to_host(c, node_lnl_out, d_lnl.p, n)))
+        return rc;
+    *n_nodes_out = count;
+    // every node is back in its post-order orientation by the restore rows' updates; one
+    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
+    double lnl;
+    return pu_run(c, &lnl, nullptr);
+}
+
+int pu_site_rates(pu_ctx *c, double *cat_post_out, double *mean_rate_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!mean_rate_out) return set_err(&c->err, PU_E_ARG, "pu_site_rates: null buffer");
+    int rc = ancestral_ready(c, "site rates");
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    int key;
+    AncArgs q = {};
+    if ((rc = edge_key(c, c->root_a, c->root_b, &key)) ||
+        (rc = edge_node_src(c, c->root_a, &q.n)) || (rc = edge_node_src(c, c->root_b, &q.o)))
+        return rc;
+    q.t = c->up_len[key];
+    const size_t S = (size_t)c->S, C = (size_t)c->C;
+    DevBuf<double> d_cat, d_rate, d_lnl;
+    if ((rc = d_cat.alloc(&c->err, cat_post_out ? S * C : 0)) ||
+        (rc = d_rate.alloc(&c->err, S)) || (rc = d_lnl.alloc(&c->err, 1)))
+        return rc;
+    q.cat_post = d_cat.p;
+    q.mean_rate = d_rate.p;
+    if ((rc = ancestral_enqueue(c, q, d_lnl.p))) return rc;
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if ((rc = ancestral_stamp(c)) ||
+        (rc = to_host(c, cat_post_out, d_cat.p, cat_post_out ? S * C : 0)) ||
+        (rc = to_host(c, mean_rate_out, d_rate.p, S)))
+        return rc;
+    return PU_OK;
+}
+
+int pu_ancestral_kernel_ms(pu_ctx *c, double *ms_out) {
+    if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
+    *ms_out = (double)c->a_ms;
+    return PU_OK;
+}
+
+}  // extern "C"

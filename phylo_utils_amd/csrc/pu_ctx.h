@@ -223,6 +223,12 @@ struct pu_ctx {
     double *h_q_res = nullptr, *d_q_res_host = nullptr;
     hipEvent_t q_ev[2] = {nullptr, nullptr};
     float q_ms = 0.f;
+    // ancestral reconstruction (pu_ancestral.hip): per-workgroup lnL sums [a_tiles], and the
+    // HIP-event time of the last k_ancestral launch when profiling
+    double *d_a_part = nullptr;
+    int a_tiles = 0;
+    hipEvent_t a_ev[2] = {nullptr, nullptr};
+    float a_ms = 0.f;
 
     // Lewis ascertainment-bias correction (tree_model.py:92-98, 151-156, 209-214): mode 0 off,
     // 1 the reference's form, 2 weighted; the dummy invariant sites are [asc_first, S)

@@ -684,6 +684,12 @@ void pu::edge_free(pu_ctx *c) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
+    dfree(c->d_a_part);
+    c->a_tiles = 0;
+    for (hipEvent_t &e : c->a_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 extern "C" {

@@ -34,7 +34,13 @@ carries, as internal node labels, the support in percent of every split over R b
 replicates (``phylo_utils_amd.bootstrap``);
 ``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
 interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
-rounds, default 50); ``-o`` then receives the final Newick.
+rounds, default 50); ``-o`` then receives the final Newick;
+``--ancestral FILE`` writes the marginal reconstruction of the N - 2 internal nodes as FASTA
+(records ``N<node index>``, one most probable state per alignment column) and ``FILE.nwk``, the
+tree with those names on its internal nodes; ``--site-rates FILE`` writes a TSV with a header and
+one row per alignment column: site (from 1), posterior mean rate, most probable rate category
+(from 1) (``phylo_utils_amd.ancestral``).  Both run on the final tree, after ``--optimise`` /
+``--nni``.
 """
 from __future__ import annotations
 
@@ -161,6 +167,12 @@ def parse_cli(argv=None):
     ap.add_argument("--nni", type=int, nargs="?", const=50, default=None, metavar="ROUNDS",
                     help="after -t or --nj: nearest-neighbour-interchange search (at most ROUNDS "
                          "rounds, default 50) before the lnL line; -o receives the final Newick")
+    ap.add_argument("--ancestral", type=str, default=None, metavar="FILE",
+                    help="write the marginal ancestral sequences of the internal nodes as FASTA "
+                         "to FILE and the tree that names them to FILE.nwk")
+    ap.add_argument("--site-rates", type=str, default=None, metavar="FILE", dest="site_rates",
+                    help="write a TSV of site, posterior mean rate and most probable rate "
+                         "category per alignment column to FILE")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -169,6 +181,9 @@ def parse_cli(argv=None):
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "ancestral", None) is not None or getattr(args, "site_rates", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--ancestral and --site-rates exclude --simulate and --distances")
     if getattr(args, "nni", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--nni excludes --simulate and --distances")
@@ -246,6 +261,21 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
+    if getattr(args, "ancestral", None) is not None:
+        seqs, newick = tm.ancestral_sequences(alphabet)
+        with open(args.ancestral, "w") as fh:
+            for name, seq in seqs.items():
+                fh.write(">{}\n".format(name))
+                for i in range(0, len(seq), 60):
+                    fh.write(seq[i:i + 60] + "\n")
+        with open(args.ancestral + ".nwk", "w") as fh:
+            fh.write(newick + "\n")
+    if getattr(args, "site_rates", None) is not None:
+        cat, rate = tm.site_rates()
+        with open(args.site_rates, "w") as fh:
+            fh.write("site\tmean_rate\tmap_category\n")
+            for i, (r, k) in enumerate(zip(rate, cat.argmax(axis=1))):
+                fh.write("{}\t{:.10g}\t{}\n".format(i + 1, r, int(k) + 1))
     lnl = tm.compute_likelihood_at_edge(*tm.traversal.root_edge).sum()
     out.write("lnL = {}\n".format(lnl))
     return lnl

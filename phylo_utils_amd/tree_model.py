@@ -601,6 +601,26 @@ class TreeModel(object):
         from . import nni
         return nni.nni_search(self, max_rounds, min_gain, sweeps, tol, method)
 
+    # ------------------------------------------------------------------ ancestral states
+    def ancestral_states(self, full=False):
+        """The most probable state of every internal node at every pattern, its posterior and,
+        with `full`, all posteriors, in one pass of the optimising traversal
+        (``ancestral.ancestral_states``, pu_ancestral_sweep)."""
+        from . import ancestral
+        return ancestral.ancestral_states(self, full)
+
+    def ancestral_sequences(self, alphabet):
+        """({"N<idx>": sequence over the alignment's columns}, the Newick that carries those
+        labels) (``ancestral.ancestral_sequences``)."""
+        from . import ancestral
+        return ancestral.ancestral_sequences(self, alphabet)
+
+    def site_rates(self):
+        """(posterior of the rate category [sites][C], mean rate [sites]) per alignment column
+        (``ancestral.site_rates``, pu_site_rates)."""
+        from . import ancestral
+        return ancestral.site_rates(self)
+
     # ------------------------------------------------------------------ simulation
     def simulate(self, n_sites, seed=0, first_site=0, return_categories=False,
                  return_ancestral=False, return_cum=False):

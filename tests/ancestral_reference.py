@@ -1,0 +1,190 @@
+"""CPU restatement of the marginal ancestral reconstruction and the site-rate posteriors
+ for the tests, composed from the oracle's own functions as tests/nni_reference.py
+is: ``tree_lnl(..., return_all=True)`` for the post-order partials, ``clv_c`` for the
+re-orientation rows, ``pmatrix``, and the formulas in numpy.  `orc` is the oracle module (the
+``oracle_mod`` fixture).  ``brute_force`` is the yardstick's own yardstick: plain enumeration of
+every joint assignment of the internal nodes, no pruning."""
+import itertools
+
+import numpy as np
+
+from nni_reference import eigen, state  # noqa: F401
+
+
+def _caterpillar(n, rng):
+    from phylo_utils_amd.tree import Node, Tree
+    cur = Node("t0", 0.2)
+    for i in range(1, n - 1):
+        p = Node(None, rng.uniform(0.05, 0.3))
+        p.add(cur)
+        p.add(Node("t%d" % i, rng.uniform(0.05, 0.3)))
+        cur = p
+    root = Node()
+    root.add(cur)
+    root.add(Node("t%d" % (n - 1), 0.2))
+    return Tree(root)
+
+
+# name: (kind, taxa, sites, categories (None: the kernel's limit), coded tips).  The smallest
+# shapes at which k_ancestral can go wrong: several tiles, a tile of one lane, one category (no
+# mix), an odd category count, the LDS limit, a root edge with a tip end, and nodes deep enough
+# to carry scalers that differ between the categories
+CASES = {
+    "dna-coded-14x700-C4": ("dna", 14, 700, 4, True),
+    "dna-dense-8x97-C1": ("dna", 8, 97, 1, False),
+    "dna-8x65-C3": ("dna", 8, 65, 3, True),
+    "binary-8x70-Cmax": ("binary", 8, 70, None, True),
+    "protein-8x97-C4": ("protein", 8, 97, 4, True),
+    "dna-pendant-root-4x70-C4": ("pendant", 4, 70, 4, True),
+    "dna-caterpillar-150x130-C4": ("caterpillar", 150, 130, 4, True),
+}
+
+
+def problem(case):
+    """dict(tree, names, codes, table, model, rm, compact, weights) of a case: GTR with unequal
+    frequencies (TwoState(0.3), LG), data simulated down the tree (no gaps), pattern weights
+    1..3."""
+    import twostate as T
+    from phylo_utils_amd import _native as N
+    from phylo_utils_amd import substitution_models as SM
+    from phylo_utils_amd.rate_models import GammaRateModel, UniformRateModel
+    from phylo_utils_amd.synthetic import (CFG2_FREQS, CFG2_GTR_RATES, make_problem,
+                                           simulate_states)
+    kind, n_taxa, n_sites, C, compact = CASES[case]
+    if C is None:
+        C = N.lib().pu_ancestral_max_cat(2)
+    rm = GammaRateModel(C, 0.8 if kind == "protein" else 0.5) if C > 1 else UniformRateModel()
+    rng = np.random.default_rng(5)
+    if kind == "binary":
+        m = T.TwoState(0.3)
+        tree, names, codes, table, _ = T.binary_problem(n_taxa, n_sites, 0.3, rm.rates, seed=2,
+                                                        ambiguous=False)
+    elif kind in ("pendant", "caterpillar"):
+        m = SM.GTR(CFG2_GTR_RATES, CFG2_FREQS)
+        tree = _caterpillar(n_taxa, rng) if kind == "caterpillar" else \
+            "(t0:0.1,t1:0.2,(t2:0.15,t3:0.3):0.25);"
+        from phylo_utils_amd.tree import prepare_tree
+        sts = simulate_states(rng, prepare_tree(tree), m, rm.rates, n_sites)
+        names = sorted(sts, key=lambda s: int(s[1:]))
+        codes, table = np.array([sts[n] for n in names], dtype=np.uint8), np.eye(4)
+    else:
+        m = SM.GTR(CFG2_GTR_RATES, CFG2_FREQS) if kind == "dna" else SM.LG()
+        tree, names, st = make_problem(n_taxa, n_sites, m, rm.rates, seed=2)
+        codes, table = st.astype(np.uint8), np.eye(len(m.freqs))
+    weights = rng.integers(1, 4, size=codes.shape[1]).astype(np.float64)
+    return dict(tree=tree, names=names, codes=codes, table=np.asarray(table), model=m, rm=rm,
+                compact=compact, weights=weights)
+
+
+def restate(orc, prob):
+    """(traversal, eigen dict, sweep(...) of a problem)."""
+    from phylo_utils_amd.tree import Traversal, prepare_tree
+    tr = Traversal(prepare_tree(prob["tree"]))
+    e = eigen(prob["model"], prob["rm"])
+    tips = {tr.names[n]: prob["table"][prob["codes"][i]] for i, n in enumerate(prob["names"])}
+    return tr, e, sweep(orc, tips, tr, e, site_weights=prob["weights"])
+
+
+def decided(post, gap=1e-9):
+    """[n][S] bool: the top two posteriors differ by more than `gap` (the MAP state is then
+    the same under any rounding the 1e-10 tolerance admits)."""
+    top = np.sort(post, axis=-1)
+    return top[..., -1] - top[..., -2] > gap
+
+
+def posterior(orc, P, S, n, o, t, e):
+    """The formulas on partials P[node] [S][C][K] and scalers S[node] [S][C] of the ends n (the
+    node reconstructed) and o of an edge of length t: (q [S][K], r [S][C], lnl [S])."""
+    pm = orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])  # [C][K][K]
+    g = e["freqs"][None, None, :] * P[n] * np.einsum("cij,scj->sci", pm, P[o])
+    F = g.sum(axis=2)
+    sigma = S[n] + S[o]
+    m = sigma.max(axis=1)
+    we = e["weights"][None, :] * np.exp(sigma - m[:, None])
+    Z = (we * F).sum(axis=1)
+    q = (we[:, :, None] * g).sum(axis=1) / Z[:, None]
+    r = we * F / Z[:, None]
+    return q, r, m + np.log(Z)
+
+
+def sweep(orc, tips, tr, e, site_weights=None):
+    """pu_ancestral_sweep and pu_site_rates on the CPU: dict(lnl of the tree, nodes [n],
+    posteriors [n][S][K], node_lnl [n], cat_post [S][C], mean_rate [S], scale [nodes][S][C] as
+    the walk left them at each node's visit (sigma of that visit: [n][S][C]))."""
+    st = state(orc, tips, tr, e, site_weights)
+    P, S = st["partials"], st["scale"]
+    sw = np.ones(P.shape[1]) if site_weights is None else np.asarray(site_weights, dtype=float)
+    internal = set(int(p) for p in tr.postorder_traversal[:, 0])
+    pm = lambda t: orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])
+    left, right = (int(v) for v in tr.root_edge)
+    _, r, _ = posterior(orc, P, S, left, right, tr.root_length(), e)
+    out = dict(lnl=st["lnl"], nodes=[], posteriors=[], node_lnl=[], sigma=[], cat_post=r,
+               mean_rate=r.dot(np.asarray(e["rates"])))
+
+    def visit(n, o):
+        if n not in internal:
+            return
+        q, _, lnl = posterior(orc, P, S, n, o, tr.brlens[n, o], e)
+        out["nodes"].append(n)
+        out["posteriors"].append(q)
+        out["node_lnl"].append(float(np.dot(sw, lnl)))
+        out["sigma"].append(S[n] + S[o])
+
+    for k, row in enumerate(tr.optimising_traversal):
+        if row[0] >= 0:
+            p, x, y = (int(v) for v in row[:3])
+            cml = np.zeros(S[p].shape)
+            P[p] = orc.clv_c(pm(tr.brlens[p, x]), pm(tr.brlens[p, y]), P[x], P[y], S[x], S[y], cml)
+            S[p] = cml
+        nod, par = int(row[3]), int(row[4])
+        if nod < 0:
+            continue
+        visit(nod, par)
+        if k == 0:
+            visit(par, nod)
+    for key in ("nodes", "posteriors", "node_lnl", "sigma"):
+        out[key] = np.array(out[key])
+    return out
+
+
+def brute_force(orc, tips, tr, e):
+    """Enumeration over all joint assignments of the internal nodes of a small tree, no pruning
+    and no scaling: dict(posteriors {node: [S][K]}, cat_post [S][C], lnl [S])."""
+    freqs, w = np.asarray(e["freqs"]), np.asarray(e["weights"])
+    K, C = len(freqs), len(w)
+    nS = next(iter(tips.values())).shape[0]
+    internal = sorted(set(int(p) for p in tr.postorder_traversal[:, 0]))
+    nbr = {}
+    for (u, v), t in tr.brlens.items():
+        nbr.setdefault(u, []).append((v, t))
+        nbr.setdefault(v, []).append((u, t))
+    # every edge directed away from the first internal node
+    start, edges, seen, todo = internal[0], [], {internal[0]}, [internal[0]]
+    while todo:
+        u = todo.pop()
+        for v, t in nbr[u]:
+            if v not in seen:
+                seen.add(v)
+                todo.append(v)
+                edges.append((u, v, orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t,
+                                                e["rates"])))
+    pos = {n: i for i, n in enumerate(internal)}
+    joint = np.zeros((nS, C) + (K,) * len(internal))
+    for x in itertools.product(range(K), repeat=len(internal)):
+        f = np.full((nS, C), freqs[x[pos[start]]])
+        for u, v, pm in edges:
+            row = pm[:, x[pos[u]], :]  # [C][K]
+            if v in pos:
+                f = f * row[None, :, x[pos[v]]]
+            else:
+                f = f * np.einsum("cj,sj->sc", row, tips[v])
+        joint[(slice(None), slice(None)) + x] = f
+    joint = joint * w.reshape((1, C) + (1,) * len(internal))
+    total = joint.reshape(nS, -1).sum(axis=1)
+    post = {}
+    for n in internal:
+        keep = 2 + pos[n]
+        axes = tuple(a for a in range(1, joint.ndim) if a != keep)
+        post[n] = joint.sum(axis=axes) / total[:, None]
+    cat = joint.reshape(nS, C, -1).sum(axis=2) / total[:, None]
+    return dict(posteriors=post, cat_post=cat, lnl=np.log(total))
