@@ -263,6 +263,45 @@ int pu_nni_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int m
                  double *scores_out, int32_t *quartets_out, int *n_scored_out);
 /* HIP-event time (ms) of the last k_quartet launch made while pu_ctx_profile was on. */
 int pu_quartet_kernel_ms(pu_ctx *ctx, double *ms_out);
+/* ---- branch support on the quartet kernel: aLRT, aBayes, SH-aLRT ----------- */
+/* site_out[3][S]: the unweighted per-pattern lnL of arrangements 0..2 at t[3] (NULL: lens[4]),
+ * -inf where no rate category gives the pattern a positive likelihood; out9 (nullable) as
+ * pu_quartet_derivs, bitwise equal to it.  Changes nothing in the context.  Refusals as
+ * pu_quartet_derivs. */
+int pu_quartet_site_lnl(pu_ctx *ctx, const int32_t nodes[4], const double lens[5],
+                        const double *t, double *site_out, double *out9);
+/* RELL sums: out[n_rep][n_vec] = B(W[r], L[v]) = sum_p W[r][p] L[v][p]; L fp64 [n_vec][n_sites],
+ * W uint32 [n_rep][n_sites] (the device form: row strides ldl, ldw >= n_sites, ldo >= n_vec,
+ * queued on `stream`).  A pattern with W[r][p] == 0 adds nothing, whatever L[v][p] is, -inf and
+ * NaN included.  The order of the sum is a function of n_sites alone (segments of 2048 patterns
+ * added serially, the segment sums added serially): out[r][v] does not depend on the other
+ * replicates or vectors of the call, on their number or position, or on the strides.  Stateless.
+ * PU_E_ARG, before any device is touched: a null buffer, n_vec, n_rep or n_sites < 1, a row
+ * stride below its row. */
+int pu_rell_sums(int device, int n_vec, int64_t n_sites, const double *L, int n_rep,
+                 const uint32_t *W, double *out);
+int pu_rell_sums_device(int device, void *stream, int n_vec, int64_t n_sites, const double *d_L,
+                        int64_t ldl, int n_rep, const uint32_t *d_W, int64_t ldw, double *d_out,
+                        int64_t ldo);
+/* pu_nni_sweep's pass with supports: scores_out / quartets_out / *n_scored_out exactly as
+ * pu_nni_sweep (bitwise).  At every scored edge one more k_quartet launch leaves the
+ * per-pattern lnL s_k of the three arrangements at their optimised lengths on the device; after
+ * the walk l_k = B(w, s_k) for the pattern weights w, and B(W[r], s_k) for replicates r =
+ * first_rep .. first_rep + n_rep - 1 of pu_boot_weights' rule on (seed, r, w), come from
+ * pu_rell_sums_device.  With d = l_0 - max(l_1, l_2), c_k = B(W[r], s_k) - l_k (-inf for an
+ * l_k that is not finite) and g_r the gap between the largest and the second largest c_k:
+ * support_out[n_scored][4] = {lrt = 2 max(d, 0), alrt_chi2 = erf(sqrt(lrt / 2)),
+ * abayes = 1 / sum_k exp(l_k - l_0), sh_alrt = #{r : d > g_r + epsilon} / n_rep}, all NaN where
+ * l_0 is not finite; rell_out (nullable) [n_scored][n_rep + 1][3] = B of row w (index 0) and of
+ * every replicate.  The context is left as pu_nni_sweep leaves it; no length is stored.
+ * Refusals as pu_nni_sweep, and PU_E_ARG, before the first launch, for n_rep < 1, a replicate
+ * outside [0, 2^32), epsilon negative or non-finite, pattern weights that are negative,
+ * non-integer or sum outside [1, 2^31 - 1].  PU_E_NOMEM (the message names the bytes) where the
+ * site buffer [n_tips - 3][3][S] does not fit; the context stays usable. */
+int pu_branch_support(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int max_iter,
+                      uint64_t seed, int64_t first_rep, int n_rep, double epsilon,
+                      double *scores_out, int32_t *quartets_out, double *support_out,
+                      double *rell_out, int *n_scored_out);
 /* ---- marginal ancestral states and site-rate posteriors -------------------- */
 /* The largest category count the ancestral kernel takes for n_states = 2, 4 or 20: its LDS use
  * of one workgroup against the 160 KiB of a CU, and no more than a context holds (64, 50, 10);

@@ -90,6 +90,12 @@ SIGNATURES = {
     "pu_quartet_derivs": (_c_int, [_P, _P, _P, _P, _P]),
     "pu_nni_sweep": (_c_int, [_P, _c_int, _P, _c_dbl, _c_int, _P, _P, _P]),
     "pu_quartet_kernel_ms": (_c_int, [_P, _P]),
+    "pu_quartet_site_lnl": (_c_int, [_P, _P, _P, _P, _P, _P]),
+    "pu_rell_sums": (_c_int, [_c_int, _c_int, _c_i64, _P, _c_int, _P, _P]),
+    "pu_rell_sums_device": (_c_int, [_c_int, _P, _c_int, _c_i64, _P, _c_i64, _c_int, _P, _c_i64,
+                                     _P, _c_i64]),
+    "pu_branch_support": (_c_int, [_P, _c_int, _P, _c_dbl, _c_int, _c_u64, _c_i64, _c_int,
+                                   _c_dbl, _P, _P, _P, _P, _P]),
     "pu_ancestral_max_cat": (_c_int, [_c_int]),
     "pu_ancestral_edge": (_c_int, [_P, _c_int, _c_int, _c_dbl, _P, _P, _P, _P]),
     "pu_ancestral_sweep": (_c_int, [_P, _c_int, _P, _P, _P, _P, _P, _P, _P]),

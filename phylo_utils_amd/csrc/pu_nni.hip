@@ -5,6 +5,9 @@
 //   pu_quartet_derivs    lnL, dlnL/dt, d2lnL/dt2 of the three arrangements of four nodes
 //   pu_nni_sweep         one pass of the optimising traversal that scores every internal edge,
 //                        the central length of each arrangement optimised by Newton
+//   pu_quartet_site_lnl  pu_quartet_derivs plus the per-pattern lnL of the three arrangements
+//   pu_branch_support    pu_nni_sweep's pass with aLRT, aBayes and SH-aLRT of every scored edge
+//                        (the RELL product is pu_rell.hip)
 //
 // Arrangement (a,b | c,d) of nodes x0..x3 with pendant lengths l0..l3 and central length t:
 //   L = clv(P(l_a), P(l_b), a, b), R = clv(P(l_c), P(l_d), c, d) -- the engine's update with
@@ -30,6 +33,7 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_service.h"
 
 using namespace pu;
 
@@ -44,6 +48,8 @@ struct QuartetArgs {
     double l[4];   // pendant lengths
     double t[3];   // central length of each arrangement
     double *part;  // [grid][9] per-workgroup sums
+    double *site;  // k_quartet<K, true>: [3][site_ld] unweighted per-pattern lnL
+    int64_t site_ld;
 };
 
 // waves per workgroup at most: K = 20 holds four K-vectors and two more per arrangement in
@@ -76,7 +82,10 @@ constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one
 __host__ __device__ constexpr int arr_c(int k) { return k == 0 ? 2 : 1; }
 __host__ __device__ constexpr int arr_d(int k) { return k == 2 ? 2 : 3; }
 
-template <int K>
+// SITES: the mix stage also stores the unweighted lnL of its 64 patterns under arrangement k,
+// smax + log(Ls) (-inf where no category has f > 0), to q.site + k * q.site_ld + site: one
+// coalesced 8-byte store per lane; the sums are formed as without it
+template <int K, bool SITES = false>
 __global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs a, QuartetArgs q) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int C = a.C;
@@ -203,6 +212,8 @@ __global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs 
             } else if (pw != 0.0) {
                 v0 = -INFINITY;  // every category has f <= 0 (lnl_node's -inf)
             }
+            if constexpr (SITES)
+                q.site[(int64_t)k * q.site_ld + site] = Ls > 0.0 ? smax + log(Ls) : -INFINITY;
         }
         v0 = wave_sum(v0);
         v1 = wave_sum(v1);
@@ -288,11 +299,17 @@ int quartet_ready(pu_ctx *c) {
 template <int K>
 void launch_quartet_k(hipStream_t st, const EdgeArgs &a, const QuartetArgs &q) {
     const dim3 grid((unsigned)a.n_tiles), block(64 * quartet_waves(K, a.C));
-    hipLaunchKernelGGL(k_quartet<K>, grid, block, quartet_lds_bytes(K, a.C), st, a, q);
+    if (q.site)
+        hipLaunchKernelGGL((k_quartet<K, true>), grid, block, quartet_lds_bytes(K, a.C), st, a, q);
+    else
+        hipLaunchKernelGGL(k_quartet<K>, grid, block, quartet_lds_bytes(K, a.C), st, a, q);
 }
 
-// one evaluation: out9[3][3] of the three arrangements of x[4] at central lengths t[3]
-int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, double *out9) {
+// one evaluation: out9[3][3] (null: not wanted, and nothing is waited for) of the three
+// arrangements of x[4] at central lengths t[3]; d_site (nullable) [3][site_ld] receives the
+// unweighted per-pattern lnL of the three (k_quartet<K, true>)
+int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, double *out9,
+                 double *d_site = nullptr, int64_t site_ld = 0) {
     EdgeArgs a;
     edge_fill_args(c, a);
     QuartetArgs q;
@@ -302,6 +319,8 @@ int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, 
     }
     for (int k = 0; k < 3; ++k) q.t[k] = t[k];
     q.part = c->d_q_part;
+    q.site = d_site;
+    q.site_ld = site_ld;
     const bool prof = c->profile;
     if (prof) {
         for (hipEvent_t &e : c->q_ev)
@@ -315,6 +334,13 @@ int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, 
     }
     HIPCHK(&c->err, hipGetLastError());
     if (prof) HIPCHK(&c->err, hipEventRecord(c->q_ev[1], c->stream));
+    if (!out9) {
+        if (prof) {
+            HIPCHK(&c->err, hipEventSynchronize(c->q_ev[1]));
+            HIPCHK(&c->err, hipEventElapsedTime(&c->q_ms, c->q_ev[0], c->q_ev[1]));
+        }
+        return PU_OK;
+    }
     hipLaunchKernelGGL(k_quartet_sum, dim3(1), dim3(256), 0, c->stream, c->d_q_part, c->n_tiles,
                        c->d_q_res_host);
     HIPCHK(&c->err, hipGetLastError());
@@ -371,6 +397,53 @@ struct Newton {
     }
 };
 
+// ---- branch support -----------------------------------------------------------
+
+// the pattern weights as a weight row of the RELL product (integers, checked on the host)
+__global__ void __launch_bounds__(256)
+    k_weight_row(const double *__restrict__ w, int64_t S, uint32_t *__restrict__ row) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s < S) row[s] = (uint32_t)w[s];
+}
+
+// one workgroup per edge e: sums [1 + n_rep][V] holds B of the pattern weights (row 0: l_k) and
+// of every replicate at vectors 3 e + k.  count[e] = #{r : d > g_r + eps}, d = l_0 - max(l_1,
+// l_2), g_r the gap between the largest and the second largest centred sum c_k = B_k - l_k; an
+// arrangement whose l_k is not finite has c_k = -inf and never wins.  Integer counts.
+__global__ void __launch_bounds__(256)
+    k_support_counts(const double *__restrict__ sums, int n_rep, int V, double eps,
+                     int32_t *__restrict__ count) {
+    __shared__ int red[4];
+    const int e = (int)blockIdx.x;
+    const double *l = sums + 3 * (size_t)e;
+    const double l0 = l[0], l1 = l[1], l2 = l[2];
+    const double d = l0 - fmax(l1, l2);
+    int cnt = 0;
+    for (int r = (int)threadIdx.x; r < n_rep; r += 256) {
+        const double *b = sums + (size_t)(r + 1) * V + 3 * (size_t)e;
+        const double c0 = isfinite(l0) ? b[0] - l0 : -INFINITY;
+        const double c1 = isfinite(l1) ? b[1] - l1 : -INFINITY;
+        const double c2 = isfinite(l2) ? b[2] - l2 : -INFINITY;
+        const double hi = fmax(c0, fmax(c1, c2));
+        const double mid = fmax(fmin(c0, c1), fmin(fmax(c0, c1), c2));
+        cnt += d > (hi - mid) + eps ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) count[e] = red[0] + red[1] + red[2] + red[3];
+}
+
+int quartet_call(pu_ctx *c, const char *fn, const int32_t *nodes, const double *lens,
+                 const double *t, double *site_out, double *out9);
+int sweep_check(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, double tol,
+                int max_iter, const double *scores_out, const int32_t *quartets_out,
+                const int *n_scored_out);
+int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, double tol,
+               int max_iter, double *scores_out, int32_t *quartets_out, int *n_scored_out,
+               double *d_site, int64_t site_ld);
+
 }  // namespace
 
 extern "C" {
@@ -384,7 +457,133 @@ int pu_quartet_max_cat(int n_states) {
 int pu_quartet_derivs(pu_ctx *c, const int32_t *nodes, const double *lens, const double *t,
                       double *out9) {
     if (!c) return set_err(nullptr, PU_E_ARG, "null context");
-    if (!nodes || !lens || !out9) return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: null buffer");
+    if (!out9) return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: null buffer");
+    return quartet_call(c, "pu_quartet_derivs", nodes, lens, t, nullptr, out9);
+}
+
+int pu_quartet_site_lnl(pu_ctx *c, const int32_t *nodes, const double *lens, const double *t,
+                        double *site_out, double *out9) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!site_out) return set_err(&c->err, PU_E_ARG, "pu_quartet_site_lnl: null buffer");
+    double tmp9[9];
+    return quartet_call(c, "pu_quartet_site_lnl", nodes, lens, t, site_out, out9 ? out9 : tmp9);
+}
+
+int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max_iter,
+                 double *scores_out, int32_t *quartets_out, int *n_scored_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    int rc = sweep_check(c, "pu_nni_sweep", n_rows, rows, tol, max_iter, scores_out, quartets_out,
+                         n_scored_out);
+    if (rc) return rc;
+    DeviceGuard g(c->device);
+    return sweep_walk(c, "pu_nni_sweep", n_rows, rows, tol, max_iter, scores_out, quartets_out,
+                      n_scored_out, nullptr, 0);
+}
+
+int pu_branch_support(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max_iter,
+                      uint64_t seed, int64_t first_rep, int n_rep, double epsilon,
+                      double *scores_out, int32_t *quartets_out, double *support_out,
+                      double *rell_out, int *n_scored_out) {
+    const char *fn = "pu_branch_support";
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!support_out) return set_err(&c->err, PU_E_ARG, "%s: null buffer", fn);
+    if (n_rep < 1) return set_err(&c->err, PU_E_ARG, "%s: n_rep = %d", fn, n_rep);
+    if (first_rep < 0 || first_rep + n_rep > ((int64_t)1 << 32))
+        return set_err(&c->err, PU_E_ARG, "%s: replicates %lld .. %lld are outside [0, 2^32)", fn,
+                       (long long)first_rep, (long long)(first_rep + n_rep - 1));
+    if (!(epsilon >= 0.0) || !std::isfinite(epsilon))
+        return set_err(&c->err, PU_E_ARG, "%s: epsilon = %g", fn, epsilon);
+    int rc = sweep_check(c, fn, n_rows, rows, tol, max_iter, scores_out, quartets_out,
+                         n_scored_out);
+    if (rc) return rc;
+    if ((int64_t)c->h_pattern_w.size() != c->S)
+        return set_err(&c->err, PU_E_STATE, "%s: the context has no pattern weights", fn);
+    int64_t N = 0;
+    for (int64_t s = 0; s < c->S; ++s) {
+        const double w = c->h_pattern_w[s];
+        if (!(w >= 0.0) || !(w <= 2147483647.0) || w != floor(w))
+            return set_err(&c->err, PU_E_ARG, "%s: pattern weight %lld = %g is not an integer in "
+                           "[0, 2^31 - 1]", fn, (long long)s, w);
+        N = std::min<int64_t>(N + (int64_t)w, (int64_t)1 << 32);
+    }
+    if (N < 1 || N > 0x7fffffff)
+        return set_err(&c->err, PU_E_ARG, "%s: the pattern weights sum to %s, outside "
+                       "[1, 2^31 - 1]", fn, N < 1 ? "0" : "more than 2^31 - 1");
+    DeviceGuard g(c->device);
+    const int cap = std::max(c->n_tips - 3, 1);
+    const int64_t S = c->S, ld = (S + 63) & ~(int64_t)63;
+    HostCall h(c->stream, &c->err);  // frees the pass's device buffers on every way out
+    // the site buffer [edge][3][ld]: the largest allocation of the pass, asked for first
+    double *d_site = h.alloc<double>((size_t)cap * 3 * ld);
+    if (h.rc) return h.rc;
+    h.rc = sweep_walk(c, fn, n_rows, rows, tol, max_iter, scores_out, quartets_out, n_scored_out,
+                      d_site, ld);
+    const int E = h.rc ? 0 : *n_scored_out, V = 3 * E;
+    if (h.rc || E == 0) return h.finish(fn);
+    // W in ranges of replicates (256 MiB); row 0 holds the pattern weights themselves
+    const int64_t RC = std::min<int64_t>(
+        n_rep, std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / (4 * (size_t)ld)) - 1));
+    uint32_t *d_W = h.alloc<uint32_t>((size_t)(RC + 1) * ld);
+    double *d_sums = h.alloc<double>((size_t)(n_rep + 1) * V);
+    int32_t *d_cnt = h.alloc<int32_t>((size_t)E);
+    if (h.rc) return h.finish(fn);
+    hipLaunchKernelGGL(k_weight_row, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream,
+                       c->d_pattern_w, S, d_W);
+    h.hip(fn, hipGetLastError());
+    for (int64_t r0 = 0; r0 < n_rep && !h.rc; r0 += RC) {
+        const int nr = (int)std::min<int64_t>(RC, n_rep - r0);
+        h.rc = pu_boot_weights_device(c->device, c->stream, seed, first_rep + r0, nr, S,
+                                      c->d_pattern_w, d_W + ld, ld);
+        if (h.rc) {
+            c->err = g_err;
+            break;
+        }
+        // the first range takes row 0 along
+        const int lead = r0 == 0 ? 1 : 0;
+        h.rc = pu_rell_sums_device(c->device, c->stream, V, S, d_site, ld, nr + lead,
+                                   d_W + (1 - lead) * ld, ld, d_sums + (size_t)(r0 + 1 - lead) * V,
+                                   V);
+        if (h.rc) c->err = g_err;
+    }
+    if (h.rc) return h.finish(fn);
+    hipLaunchKernelGGL(k_support_counts, dim3((unsigned)E), dim3(256), 0, c->stream, d_sums, n_rep,
+                       V, epsilon, d_cnt);
+    h.hip(fn, hipGetLastError());
+    std::vector<double> sums((size_t)(n_rep + 1) * V);
+    std::vector<int32_t> cnt((size_t)E);
+    h.to_host(sums.data(), d_sums, sums.size());
+    h.to_host(cnt.data(), d_cnt, cnt.size());
+    if ((rc = h.finish(fn))) return rc;
+    for (int e = 0; e < E; ++e) {
+        const double *l = sums.data() + 3 * (size_t)e;
+        double *o = support_out + 4 * (size_t)e;
+        if (!std::isfinite(l[0])) {
+            o[0] = o[1] = o[2] = o[3] = NAN;
+        } else {
+            const double d = l[0] - std::max(l[1], l[2]);
+            o[0] = 2.0 * std::max(d, 0.0);
+            o[1] = erf(sqrt(o[0] / 2.0));
+            o[2] = 1.0 / (1.0 + exp(l[1] - l[0]) + exp(l[2] - l[0]));
+            o[3] = (double)cnt[e] / (double)n_rep;
+        }
+        if (rell_out)
+            for (int r = 0; r <= n_rep; ++r)
+                for (int k = 0; k < 3; ++k)
+                    rell_out[((size_t)e * (n_rep + 1) + r) * 3 + k] =
+                        sums[(size_t)r * V + 3 * e + k];
+    }
+    return PU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// pu_quartet_derivs and pu_quartet_site_lnl: the checks, then one evaluation; site_out (host,
+// nullable) [3][S]
+int quartet_call(pu_ctx *c, const char *fn, const int32_t *nodes, const double *lens,
+                 const double *t, double *site_out, double *out9) {
+    if (!nodes || !lens) return set_err(&c->err, PU_E_ARG, "%s: null buffer", fn);
     int rc = quartet_ready(c);
     if (rc) return rc;
     DeviceGuard g(c->device);
@@ -392,33 +591,44 @@ int pu_quartet_derivs(pu_ctx *c, const int32_t *nodes, const double *lens, const
     for (int i = 0; i < 4; ++i) {
         for (int j = 0; j < i; ++j)
             if (nodes[i] == nodes[j])
-                return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: node %d repeated", nodes[i]);
+                return set_err(&c->err, PU_E_ARG, "%s: node %d repeated", fn, nodes[i]);
         if ((rc = edge_node_src(c, nodes[i], &x[i]))) return rc;
     }
     for (int i = 0; i < 5; ++i)
         if (!(lens[i] > 0.0) || !std::isfinite(lens[i]))
-            return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: length %d = %g", i, lens[i]);
+            return set_err(&c->err, PU_E_ARG, "%s: length %d = %g", fn, i, lens[i]);
     double tt[3] = {lens[4], lens[4], lens[4]};
     if (t)
         for (int k = 0; k < 3; ++k) {
             if (!(t[k] > 0.0) || !std::isfinite(t[k]))
-                return set_err(&c->err, PU_E_ARG, "pu_quartet_derivs: central length %d = %g", k,
-                               t[k]);
+                return set_err(&c->err, PU_E_ARG, "%s: central length %d = %g", fn, k, t[k]);
             tt[k] = t[k];
         }
-    return quartet_eval(c, x, lens, tt, out9);
+    if (!site_out) return quartet_eval(c, x, lens, tt, out9);
+    HostCall h(c->stream, &c->err);
+    double *d_site = h.alloc<double>(3 * (size_t)c->S);
+    if (!h.rc) h.rc = quartet_eval(c, x, lens, tt, out9, d_site, c->S);
+    h.to_host(site_out, d_site, 3 * (size_t)c->S);
+    return h.finish(fn);
 }
 
-int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max_iter,
-                 double *scores_out, int32_t *quartets_out, int *n_scored_out) {
-    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+// the argument rules and refusals of a scoring pass
+int sweep_check(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, double tol,
+                int max_iter, const double *scores_out, const int32_t *quartets_out,
+                const int *n_scored_out) {
     if (n_rows < 1 || !rows || !scores_out || !quartets_out || !n_scored_out)
-        return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: no rows or a null buffer");
+        return set_err(&c->err, PU_E_ARG, "%s: no rows or a null buffer", fn);
     if (!(tol > 0.0) || max_iter < 0)
-        return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: tol %g, max_iter %d", tol, max_iter);
-    int rc = quartet_ready(c);
-    if (rc) return rc;
-    DeviceGuard g(c->device);
+        return set_err(&c->err, PU_E_ARG, "%s: tol %g, max_iter %d", fn, tol, max_iter);
+    return quartet_ready(c);
+}
+
+// the scoring pass of pu_nni_sweep; with d_site, every scored edge also leaves the per-pattern
+// lnL of its three arrangements at their optimised lengths in d_site [edge][3][site_ld]
+int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, double tol,
+               int max_iter, double *scores_out, int32_t *quartets_out, int *n_scored_out,
+               double *d_site, int64_t site_ld) {
+    int rc;
     // the children of every internal node, in the caller's order (pu_set_schedule's ops)
     std::vector<int> child(2 * (size_t)c->n_nodes, -1);
     for (int o = 0; o < c->n_ops; ++o) {
@@ -446,15 +656,15 @@ int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max
                               row[0] >= 0 ? row[1] : child[2 * (size_t)par],
                               row[0] >= 0 ? row[2] : child[2 * (size_t)par + 1]};
         if (n_scored >= cap)
-            return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: more than n_tips - 3 = %d internal "
-                           "edges in the rows", cap);
+            return set_err(&c->err, PU_E_ARG, "%s: more than n_tips - 3 = %d internal "
+                           "edges in the rows", fn, cap);
         NodeSrc x[4];
         double l[4];
         for (int i = 0; i < 4; ++i) {
             int key;
             if (nodes[i] < 0)
-                return set_err(&c->err, PU_E_ARG, "pu_nni_sweep: node %d has no children in the "
-                               "schedule", i < 2 ? nod : par);
+                return set_err(&c->err, PU_E_ARG, "%s: node %d has no children in the "
+                               "schedule", fn, i < 2 ? nod : par);
             if ((rc = edge_node_src(c, nodes[i], &x[i])) ||
                 (rc = edge_key(c, nodes[i], i < 2 ? nod : par, &key)))
                 return rc;
@@ -481,6 +691,12 @@ int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max
         qo[0] = nod;
         qo[1] = par;
         for (int i = 0; i < 4; ++i) qo[2 + i] = nodes[i];
+        if (d_site) {  // one more launch at (t*_0, t*_1, t*_2); nothing comes back to the host
+            for (int k = 0; k < 3; ++k) t[k] = nt[k].t;
+            if ((rc = quartet_eval(c, x, l, t, nullptr, d_site + (size_t)n_scored * 3 * site_ld,
+                                   site_ld)))
+                return rc;
+        }
         ++n_scored;
     }
     *n_scored_out = n_scored;
@@ -489,6 +705,10 @@ int pu_nni_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, int max
     double lnl;
     return pu_run(c, &lnl, nullptr);
 }
+
+}  // namespace
+
+extern "C" {
 
 int pu_quartet_kernel_ms(pu_ctx *c, double *ms_out) {
     if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");

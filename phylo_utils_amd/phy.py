@@ -35,6 +35,11 @@ replicates (``phylo_utils_amd.bootstrap``);
 ``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
 interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
 rounds, default 50); ``-o`` then receives the final Newick;
+``--support [R]`` (after ``-t`` or ``--nj``, and after ``--nni`` when given) labels every internal
+edge of the final tree with ``SH-aLRT/aBayes`` -- percent with one decimal over R RELL replicates
+(default 1000, the seed of ``--seed``) and probability with three (``phylo_utils_amd.support``)
+-- on optimised branch lengths (one pass of ``--optimiser`` where neither ``--optimise`` nor
+``--nni`` has optimised them), and writes that Newick to ``-o``;
 ``--ancestral FILE`` writes the marginal reconstruction of the N - 2 internal nodes as FASTA
 (records ``N<node index>``, one most probable state per alignment column) and ``FILE.nwk``, the
 tree with those names on its internal nodes; ``--site-rates FILE`` writes a TSV with a header and
@@ -167,6 +172,10 @@ def parse_cli(argv=None):
     ap.add_argument("--nni", type=int, nargs="?", const=50, default=None, metavar="ROUNDS",
                     help="after -t or --nj: nearest-neighbour-interchange search (at most ROUNDS "
                          "rounds, default 50) before the lnL line; -o receives the final Newick")
+    ap.add_argument("--support", type=int, nargs="?", const=1000, default=None, metavar="R",
+                    help="after -t or --nj (and --nni): label the internal edges of the final "
+                         "tree with SH-aLRT/aBayes supports over R RELL replicates (default "
+                         "1000; seed: --seed); -o receives the labelled Newick")
     ap.add_argument("--ancestral", type=str, default=None, metavar="FILE",
                     help="write the marginal ancestral sequences of the internal nodes as FASTA "
                          "to FILE and the tree that names them to FILE.nwk")
@@ -189,6 +198,11 @@ def validate_args(args):
             raise ValueError("--nni excludes --simulate and --distances")
         if args.nni < 0:
             raise ValueError("--nni needs a non-negative number of rounds")
+    if getattr(args, "support", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--support excludes --simulate and --distances")
+        if args.support < 1:
+            raise ValueError("--support needs at least one replicate")
     if getattr(args, "bootstrap", None) is not None:
         if getattr(args, "nj", None) is None:
             raise ValueError("--bootstrap needs --nj")
@@ -258,6 +272,18 @@ def run(args, out=None):
     if getattr(args, "nni", None) is not None:
         tree, _, _ = tm.nni_search(max_rounds=args.nni, sweeps=max(args.optimise, 1),
                                    method=args.optimiser)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
+    if getattr(args, "support", None) is not None:
+        from .support import label_tree, support_label
+        from .tree import with_lengths
+        if not args.optimise and getattr(args, "nni", None) is None:
+            tm.optimise_branch_lengths(sweeps=1, method=args.optimiser)
+        quartets, _, sup = tm.branch_support(n_replicates=args.support, seed=args.seed)
+        tree = label_tree(with_lengths(tm.tree, tm.traversal.brlens), quartets,
+                          list(zip(sup["sh_alrt"], sup["abayes"])),
+                          lambda v: support_label(*v))
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")

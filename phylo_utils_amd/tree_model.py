@@ -601,6 +601,22 @@ class TreeModel(object):
         from . import nni
         return nni.nni_search(self, max_rounds, min_gain, sweeps, tol, method)
 
+    def quartet_site_lnl(self, nodes, lens, t=None):
+        """The unweighted per-pattern lnL of the three arrangements of four nodes, and their
+        {lnL, d1, d2} (``support.quartet_site_lnl``, pu_quartet_site_lnl): (site [3][S],
+        out [3][3])."""
+        from . import support
+        return support.quartet_site_lnl(self, nodes, lens, t)
+
+    def branch_support(self, n_replicates=1000, seed=0, epsilon=0.05, tol=1e-8, max_iter=50,
+                       first_replicate=0, full=False):
+        """aLRT, aBayes and SH-aLRT of every internal edge in one scoring pass
+        (``support.branch_support``, pu_branch_support): (quartets, scores, support dict of
+        lrt, alrt_chi2, abayes, sh_alrt [n])."""
+        from . import support
+        return support.branch_support(self, n_replicates, seed, epsilon, tol, max_iter,
+                                      first_replicate, full)
+
     # ------------------------------------------------------------------ ancestral states
     def ancestral_states(self, full=False):
         """The most probable state of every internal node at every pattern, its posterior and,
