@@ -337,6 +337,44 @@ int pu_ancestral_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *no
 int pu_site_rates(pu_ctx *ctx, double *cat_post_out, double *mean_rate_out);
 /* HIP-event time (ms) of the last k_ancestral launch made while pu_ctx_profile was on. */
 int pu_ancestral_kernel_ms(pu_ctx *ctx, double *ms_out);
+/* ---- per-edge joint count matrices (the reference has none) ------------------- */
+/* The largest category count the counts kernel takes for n_states = 2, 4 or 20: its LDS use of
+ * one workgroup against the 160 KiB of a CU, no more than a context holds and, for 20 states,
+ * one category per wave (64, 64, 6); PU_E_ARG for other n_states.  Host only.  (The reference
+ * has none) */
+int pu_counts_max_cat(int n_states);
+/* The joint count matrices of one edge from the current partials of `node` (the subtree on its
+ * side of the edge; it may be a tip) and of `other` (everything else), at `length` (< 0: the
+ * edge's current length), like pu_edge_lnl on the nodes' CURRENT partials:
+ *   counts_out[c][i][j] = sum_s pw_s (w_c e^{sigma_sc - m_s} / Z_s) A_sc(i) B_sc(j),
+ * i the state at `node`, j the state at `other`, A and B their vectors, sigma the sum of their
+ * scalers, m its maximum over the categories, Z the mixed site likelihood, pw the pattern
+ * weight: the derivative of lnL in every entry of pi_j P_c(length)[j][i].  *lnl_out is the
+ * pattern-weighted lnL.  A pattern of weight 0 adds exactly nothing; a pattern of non-zero
+ * weight and likelihood 0 makes *lnl_out -inf and leaves the matrices unspecified.  Bitwise
+ * reproducible; changes nothing in the context.  PU_KEEP_PARTIALS contexts on the device
+ * eigen-system (a reversible model) without an ascertainment correction (else PU_E_STATE);
+ * PU_E_ARG: a null buffer, a node out of range, nodes not joined by an edge, a zero or
+ * non-finite length, more categories than pu_counts_max_cat.  (The reference has none; DESIGN
+ * 4.18.) */
+int pu_edge_counts(pu_ctx *ctx, int node, int other, double length, double *counts_out,
+                   double *lnl_out);
+/* Every edge in one pass over the optimising traversal (rows as pu_optimise_sweep takes them,
+ * lengths the context's current ones).  Every re-orientation / restore row is applied; every
+ * row with NOD >= 0 yields the matrices of edge (NOD, PAR), tip edges included, each edge once
+ * and in that order: edges_out[n][2] = (NOD, PAR), lengths_out[n], counts_out[n][C][K][K] (i
+ * the state at NOD, j at PAR, the end towards the root edge), edge_lnl_out[n] (every entry the
+ * tree's lnL, by the pulley principle), *n_edges_out = n <= 2 n_tips - 3; the buffers hold
+ * 2 n_tips - 3 entries, more edges in the rows are PU_E_ARG.  The results stay on the device
+ * during the pass and are copied once per array.  The pass ends with a full traversal, so the
+ * context's partials, lnL and sitewise lnL are bitwise those of pu_run before the call.
+ * Refusals as pu_edge_counts.  (The reference has none) */
+int pu_counts_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *edges_out,
+                    double *lengths_out, double *counts_out, double *edge_lnl_out,
+                    int *n_edges_out);
+/* HIP-event time (ms) of the last k_counts launch made while pu_ctx_profile was on.  (The
+ * reference has none) */
+int pu_counts_kernel_ms(pu_ctx *ctx, double *ms_out);
 /* Current lengths in pu_set_schedule's layout: brlens_out[n_ops][2], root length. */
 int pu_get_branch_lengths(pu_ctx *ctx, double *brlens_out, double *root_len_out);
 

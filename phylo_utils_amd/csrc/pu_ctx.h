@@ -229,6 +229,12 @@ struct pu_ctx {
     int a_tiles = 0;
     hipEvent_t a_ev[2] = {nullptr, nullptr};
     float a_ms = 0.f;
+    // per-edge joint counts (pu_counts.hip): the workgroups' partial matrices and lnL sums
+    // [c_part_cap] doubles, and the HIP-event time of the last k_counts launch when profiling
+    double *d_c_part = nullptr;
+    size_t c_part_cap = 0;
+    hipEvent_t c_ev[2] = {nullptr, nullptr};
+    float c_ms = 0.f;
 
     // Lewis ascertainment-bias correction (tree_model.py:92-98, 151-156, 209-214): mode 0 off,
     // 1 the reference's form, 2 weighted; the dummy invariant sites are [asc_first, S)

@@ -690,6 +690,12 @@ void pu::edge_free(pu_ctx *c) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
+    dfree(c->d_c_part);
+    c->c_part_cap = 0;
+    for (hipEvent_t &e : c->c_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 extern "C" {

@@ -45,7 +45,14 @@ edge of the final tree with ``SH-aLRT/aBayes`` -- percent with one decimal over 
 tree with those names on its internal nodes; ``--site-rates FILE`` writes a TSV with a header and
 one row per alignment column: site (from 1), posterior mean rate, most probable rate category
 (from 1) (``phylo_utils_amd.ancestral``).  Both run on the final tree, after ``--optimise`` /
-``--nni``.
+``--nni``;
+``--fit [LIST]`` (after ``--nj`` / ``--nni`` / ``--optimise``, before ``--support`` / ``--ancestral``
+/ ``--site-rates``) fits the model parameters in the comma-separated LIST -- default: every free
+parameter of the ``-m`` model (``rates``, ``kappa``, ``alpha_y``, ``alpha_r``, ``freqs``,
+``alpha``) -- jointly with all branch lengths on the exact gradient
+(``phylo_utils_amd.modelfit``), prints one extra line ``model = <string>`` before ``lnL = ``, the
+fitted model in the grammar above (``%.10g``) so that ``-m`` reads it back, and writes the tree
+with the fitted lengths to ``-o``.
 """
 from __future__ import annotations
 
@@ -182,6 +189,11 @@ def parse_cli(argv=None):
     ap.add_argument("--site-rates", type=str, default=None, metavar="FILE", dest="site_rates",
                     help="write a TSV of site, posterior mean rate and most probable rate "
                          "category per alignment column to FILE")
+    ap.add_argument("--fit", type=str, nargs="?", const="", default=None, metavar="LIST",
+                    help="fit the model parameters in the comma-separated LIST (default: every "
+                         "free parameter of the -m model) jointly with all branch lengths, "
+                         "after --optimise / --nni; prints a 'model = ' line that -m reads back; "
+                         "-o receives the Newick with the fitted lengths")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -193,6 +205,11 @@ def validate_args(args):
     if getattr(args, "ancestral", None) is not None or getattr(args, "site_rates", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--ancestral and --site-rates exclude --simulate and --distances")
+    if getattr(args, "fit", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--fit excludes --simulate and --distances")
+        if getattr(args, "ascertainment", None):
+            raise ValueError("--fit with --ascertainment is not implemented")
     if getattr(args, "nni", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--nni excludes --simulate and --distances")
@@ -275,6 +292,17 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
+    fitted = None
+    if getattr(args, "fit", None) is not None:
+        from . import modelfit
+        from .tree import with_lengths
+        names = [x for x in args.fit.split(",") if x] or \
+            modelfit.free_parameters(tm.substitution_model, tm.rate_model)
+        tm.optimise_model(params=names, branch_lengths=True)
+        fitted = modelfit.model_string(tm.substitution_model, tm.rate_model)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(with_lengths(tm.tree, tm.traversal.brlens).as_newick() + "\n")
     if getattr(args, "support", None) is not None:
         from .support import label_tree, support_label
         from .tree import with_lengths
@@ -303,6 +331,8 @@ def run(args, out=None):
             for i, (r, k) in enumerate(zip(rate, cat.argmax(axis=1))):
                 fh.write("{}\t{:.10g}\t{}\n".format(i + 1, r, int(k) + 1))
     lnl = tm.compute_likelihood_at_edge(*tm.traversal.root_edge).sum()
+    if fitted is not None:
+        out.write("model = {}\n".format(fitted))
     out.write("lnL = {}\n".format(lnl))
     return lnl
 

@@ -637,6 +637,28 @@ class TreeModel(object):
         from . import ancestral
         return ancestral.site_rates(self)
 
+    # ------------------------------------------------------------------ gradients, model fitting
+    def edge_counts(self):
+        """The joint count matrices of every edge in one pass of the optimising traversal
+        (``gradient.edge_counts``, pu_counts_sweep)."""
+        from . import gradient
+        return gradient.edge_counts(self)
+
+    def gradient(self, params=(), branch_lengths=True):
+        """(dict name -> dlnL/dparam, dict (nod, par) -> dlnL/dt or None) from one pass of the
+        count kernel (``gradient.model_gradient`` / ``gradient.branch_gradient``)."""
+        from . import gradient
+        res = gradient.edge_counts(self)
+        return (gradient.model_gradient(self, params, res) if params else {},
+                gradient.branch_gradient(self, res) if branch_lengths else None)
+
+    def optimise_model(self, params=("alpha", "rates", "freqs"), branch_lengths=True,
+                       max_iter=200, lnl_tol=1e-6):
+        """Fit the named model parameters and, when asked, all branch lengths jointly
+        (``modelfit.optimise_model``)."""
+        from . import modelfit
+        return modelfit.optimise_model(self, params, branch_lengths, max_iter, lnl_tol)
+
     # ------------------------------------------------------------------ simulation
     def simulate(self, n_sites, seed=0, first_site=0, return_categories=False,
                  return_ancestral=False, return_cum=False):

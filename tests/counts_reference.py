@@ -1,0 +1,162 @@
+"""CPU restatement of the per-edge joint count matrices and the gradients built on them (DESIGN
+4.18) for the tests, composed like tests/ancestral_reference.py (whose ``state``, ``eigen``,
+``problem`` and ``CASES`` it imports): the same walk with ``clv_c`` and ``pmatrix``, M from its
+definition with ``np.einsum``, and formulas (1)-(3) with dP/dtheta taken by central differences
+OF P ON THE HOST -- independent of the Frechet formula of phylo_utils_amd/gradient.py.  `orc` is
+the oracle module (the ``oracle_mod`` fixture)."""
+import copy
+
+import numpy as np
+
+from ancestral_reference import CASES, eigen, problem, state  # noqa: F401
+
+H = 1e-6  # step of the central differences of the oracle's lnL
+# step of the central differences of P, pi and w: the five-point rule (8 (f(h) - f(-h)) -
+# (f(2h) - f(-2h))) / 12h, truncation h^4 f^(5) / 30 ~ 3e-14, rounding 1.5 eps / h ~ 2e-13 per
+# entry of P -- the three-point rule at any step leaves ~1e-10 per entry, which the sum over
+# edges, categories and states of M (entries up to sum pw) lifts above the 1e-8 the gradient
+# tests ask for
+H_P = 1e-3
+
+
+def counts_of(orc, P, S, n, o, t, e, sw):
+    """(M [C][K][K], lnl) of edge (n, o): i the state at n, j at o, pi on o's side."""
+    pm = orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])  # [C][K][K]
+    X = e["freqs"][None, :, None] * pm  # [c][j][i] = pi_j P_c[j][i]
+    F = np.einsum("sci,scj,cji->sc", P[n], P[o], X)
+    sigma = S[n] + S[o]
+    m = sigma.max(axis=1)
+    we = e["weights"][None, :] * np.exp(sigma - m[:, None])
+    Z = (we * F).sum(axis=1)
+    coef = sw[:, None] * we / Z[:, None]
+    return np.einsum("sc,sci,scj->cij", coef, P[n], P[o]), float(np.dot(sw, m + np.log(Z)))
+
+
+def sweep(orc, tips, tr, e, site_weights=None):
+    """pu_counts_sweep on the CPU: dict(lnl of the tree, edges [n][2] (NOD, PAR), lengths [n],
+    counts [n][C][K][K], edge_lnl [n])."""
+    st = state(orc, tips, tr, e, site_weights)
+    P, S = st["partials"], st["scale"]
+    sw = np.ones(P.shape[1]) if site_weights is None else np.asarray(site_weights, dtype=float)
+    pm = lambda t: orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])
+    out = dict(lnl=st["lnl"], edges=[], lengths=[], counts=[], edge_lnl=[])
+    for row in tr.optimising_traversal:
+        if row[0] >= 0:
+            p, x, y = (int(v) for v in row[:3])
+            cml = np.zeros(S[p].shape)
+            P[p] = orc.clv_c(pm(tr.brlens[p, x]), pm(tr.brlens[p, y]), P[x], P[y], S[x], S[y], cml)
+            S[p] = cml
+        nod, par = int(row[3]), int(row[4])
+        if nod < 0:
+            continue
+        t = tr.brlens[nod, par]
+        M, lnl = counts_of(orc, P, S, nod, par, t, e, sw)
+        out["edges"].append((nod, par))
+        out["lengths"].append(t)
+        out["counts"].append(M)
+        out["edge_lnl"].append(lnl)
+    out["edges"] = np.array(out["edges"], dtype=np.int32)
+    for key in ("lengths", "counts", "edge_lnl"):
+        out[key] = np.array(out[key])
+    return out
+
+
+def restate(orc, prob):
+    """(traversal, eigen dict, tips, sweep(...)) of a problem."""
+    from phylo_utils_amd.tree import Traversal, prepare_tree
+    tr = Traversal(prepare_tree(prob["tree"]))
+    e = eigen(prob["model"], prob["rm"])
+    tips = {tr.names[n]: prob["table"][prob["codes"][i]] for i, n in enumerate(prob["names"])}
+    return tr, e, tips, sweep(orc, tips, tr, e, site_weights=prob["weights"])
+
+
+def invariant(ref_or_dev, e, orc):
+    """[n]: sum_c sum_ij M[c][i][j] pi_j P_c(t_e)[j][i] of every edge; each equals sum pw."""
+    out = []
+    for M, t in zip(ref_or_dev["counts"], ref_or_dev["lengths"]):
+        pm = orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])
+        out.append(np.einsum("cij,j,cji->", M, e["freqs"], pm))
+    return np.array(out)
+
+
+# ---------------------------------------------------------------- parameters and their shifts
+def shifted(prob, tr, name, delta):
+    """(model, rate model, traversal) with parameter `name` moved by `delta`.  Names: "alpha";
+    ("rates", k) the k-th GTR exchangeability, GT held at its value; ("freqs", k) pi_k, the last
+    frequency taking up the difference; "kappa" (HKY85); ("length", (a, b))."""
+    from phylo_utils_amd import substitution_models as SM
+    from phylo_utils_amd.rate_models import GammaRateModel
+    m, rm, tr2 = prob["model"], prob["rm"], tr
+    if name == "alpha":
+        rm = GammaRateModel(rm.ncat, rm.alpha + delta)
+    elif name == "kappa":
+        m = SM.HKY85(m._alpha_y + delta, m.freqs)
+    elif name[0] == "rates":
+        r = np.array(m.rates[SM._UPPER], dtype=float)
+        r[name[1]] += delta
+        m = SM.GTR(r, m.freqs)
+    elif name[0] == "freqs":
+        f = np.array(m.freqs, dtype=float)
+        f[name[1]] += delta
+        f[-1] -= delta
+        if isinstance(m, SM.GTR):
+            m = SM.GTR(m.rates, f)
+        elif isinstance(m, SM.HKY85):
+            m = SM.HKY85(m._alpha_y, f)
+        else:  # the published protein frequencies are used as stored, unchecked (LG: 1.000001)
+            m = copy.copy(m)
+            m._freqs = f
+            m._q_mtx = SM.compute_q_matrix(m._rates, f)
+            m.eigen = SM.Eigen(*SM.get_eigen(m._q_mtx, f))
+    elif name[0] == "length":
+        tr2 = copy.copy(tr)
+        tr2.brlens = type(tr.brlens)(tr.brlens)
+        tr2.brlens[tuple(sorted(name[1]))] = tr.brlens[name[1]] + delta
+    else:
+        raise ValueError(name)
+    return m, rm, tr2
+
+
+def lnl_at(orc, prob, tips, tr, name, delta):
+    """The oracle's lnL with parameter `name` moved by `delta`."""
+    m, rm, tr2 = shifted(prob, tr, name, delta)
+    return state(orc, tips, tr2, eigen(m, rm), prob["weights"])["lnl"]
+
+
+def fd_gradient(orc, prob, tips, tr, name, h=H):
+    """Central difference of the oracle's lnL in `name`."""
+    return (lnl_at(orc, prob, tips, tr, name, h) - lnl_at(orc, prob, tips, tr, name, -h)) / (2 * h)
+
+
+def gradient(orc, prob, tr, ref, name, h=H_P):
+    """dlnL/d`name` from the count matrices `ref` (the restatement's or the device's) by
+    formulas (1)-(3), dP/dtheta, dpi/dtheta and dw/dtheta by central differences of P, pi and w
+    on the host."""
+    def parts(delta):
+        m, rm, tr2 = shifted(prob, tr, name, delta)
+        e = eigen(m, rm)
+        P = np.array([orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], tr2.brlens[int(a), int(b)],
+                                  e["rates"]) for a, b in ref["edges"]])  # [e][c][j][i]
+        return P, e["freqs"], e["weights"]
+    p1, m1, p2, m2 = parts(h), parts(-h), parts(2 * h), parts(-2 * h)
+    dP, dpi, dw = ((8.0 * (a - b) - (c - d)) / (12.0 * h) for a, b, c, d in zip(p1, m1, p2, m2))
+    e0 = eigen(prob["model"], prob["rm"])
+    pi, w = e0["freqs"], e0["weights"]
+    M = ref["counts"]
+    P0 = orc.pmatrix(e0["evecs"], e0["evals"], e0["ivecs"], ref["lengths"][0], e0["rates"])
+    g = np.einsum("ecij,j,ecji->", M, pi, dP)                       # (1)
+    g += np.einsum("cij,j,cji->", M[0], dpi, P0)                    # (2)
+    g += np.einsum("c,cij,j,cji->", dw / w, M[0], pi, P0)           # (3)
+    return float(g)
+
+
+def branch_gradient(orc, prob, ref, h=H_P):
+    """[n] dlnL/dt of every edge of `ref` by formula (1): only that edge's P moves, dP/dt by the
+    five-point central difference of pmatrix."""
+    e = eigen(prob["model"], prob["rm"])
+    pm = lambda t: orc.pmatrix(e["evecs"], e["evals"], e["ivecs"], t, e["rates"])
+    out = []
+    for M, t in zip(ref["counts"], ref["lengths"]):
+        dP = (8.0 * (pm(t + h) - pm(t - h)) - (pm(t + 2 * h) - pm(t - 2 * h))) / (12.0 * h)
+        out.append(np.einsum("cij,j,cji->", M, e["freqs"], dP))
+    return np.array(out)
