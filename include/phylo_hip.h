@@ -375,6 +375,68 @@ int pu_counts_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *edges
 /* HIP-event time (ms) of the last k_counts launch made while pu_ctx_profile was on.  (The
  * reference has none) */
 int pu_counts_kernel_ms(pu_ctx *ctx, double *ms_out);
+/* ---- phylogenetic placement of query sequences (the reference has none) ------- */
+/* A query q joins edge (n, o) of length t at its midpoint on a pendant branch of length l.  With
+ * A, B the current vectors of the two ends at (pattern p, category c), sA, sB their scalers and
+ * z the query's tip vector at a site, a row of code_table[n_codes][K]:
+ *   a_pc(i)    = pi_i [P_c(t/2) A_pc](i) [P_c(t/2) B_pc](i)
+ *   sigma_pc   = sA_pc + sB_pc,  m_p = max_c sigma_pc (categories with sum_i a_pc(i) > 0)
+ *   F_p(l, z)  = sum_c w_c e^{sigma_pc - m_p} sum_i a_pc(i) [P_c(l) z](i)
+ *   lnL(q,e,l) = sum_s sw_s (m_p(s) + log F_p(s)(l, z_qs))
+ * the lnL of the tree with e split into halves and q hung from the new node (pulley principle).
+ * Queries: query_codes[n_query][n_sites] uint8 into code_table (n_codes <= 32); site_pattern
+ * [n_sites] the context pattern of every query column (NULL: the identity, n_sites = the
+ * context's patterns); site_weight[n_sites] (NULL: 1).  A site of weight 0 adds nothing; one of
+ * non-zero weight and F <= 0 makes the sum -inf.  Every call is bitwise reproducible, and a
+ * query's numbers do not depend on the other queries of the call.
+ * Common refusals, all before any launch: PU_KEEP_PARTIALS contexts on the device eigen-system
+ * (a reversible model) without an ascertainment correction (else PU_E_STATE); PU_E_ARG: a null
+ * buffer, n_query or n_sites < 1, n_codes outside [1, 32], a code >= n_codes, a site_pattern
+ * entry outside [0, patterns), n_sites != patterns with a NULL map, l0 not finite or <= 0, tol
+ * negative, max_iter < 0, more categories than pu_place_max_cat. */
+/* The largest category count the placement kernels take for n_states = 2, 4 or 20: the table
+ * kernel's LDS use of one workgroup against the 160 KiB of a CU, and no more than a context
+ * holds; PU_E_ARG for other n_states.  Host only. */
+int pu_place_max_cat(int n_states);
+/* All queries at one edge, on the CURRENT partials of `node` and `other` (like pu_edge_counts)
+ * at `length` (finite and > 0, else PU_E_ARG): score_out[Q] = lnL(q, e, l0), the pre-score;
+ * then, from l0, pu_optimise_edge's Newton rule on l (bounds [1e-8, 100], `tol`, at most
+ * max_iter steps) in the kernel: pendant_out[Q] = l*, lnl_out[Q] = lnL(l*), derivs_out[Q][2] =
+ * dlnL/dl and d2lnL/dl2 at l*.  max_iter = 0 gives the pre-score alone: lnl_out = score_out,
+ * pendant_out = l0, derivs_out NaN.  Changes nothing in the context. */
+int pu_place_edge(pu_ctx *ctx, int node, int other, double length, int n_query, int64_t n_sites,
+                  const uint8_t *query_codes, const int32_t *site_pattern,
+                  const double *site_weight, int n_codes, const double *code_table, double l0,
+                  double tol, int max_iter, double *score_out, double *pendant_out,
+                  double *lnl_out, double *derivs_out);
+/* The pre-score of every query at every edge in one pass over the optimising traversal (rows
+ * and edge order as pu_counts_sweep: every row with NOD >= 0, tip edges included, each edge
+ * once): edges_out[E][2] = (NOD, PAR), lengths_out[E], score_out[E][Q] = lnL(q, e, l0),
+ * *n_edges_out = E <= 2 n_tips - 3; the buffers hold 2 n_tips - 3 edges, more in the rows are
+ * PU_E_ARG.  The queries are uploaded once; the scores stay on the device during the pass and
+ * are copied once.  The pass ends with a full traversal, so the context's partials, lnL and
+ * sitewise lnL are bitwise those of pu_run before the call. */
+int pu_place_prescore(pu_ctx *ctx, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
+                      const uint8_t *query_codes, const int32_t *site_pattern,
+                      const double *site_weight, int n_codes, const double *code_table, double l0,
+                      int32_t *edges_out, double *lengths_out, double *score_out,
+                      int *n_edges_out);
+/* The same pass with the Newton rule of pu_place_edge for chosen (edge, query) pairs: at edge
+ * number n of the pass (pu_place_prescore's order) the queries cand_query[cand_off[n] ..
+ * cand_off[n + 1]) are optimised from l0; cand_off[n_edges + 1] starts at 0 and does not
+ * decrease.  Per candidate: pendant_out, lnl_out, derivs_out[.][2], iters_out (Newton steps).
+ * An edge with an empty list launches nothing beyond the pass's own rows.  PU_E_ARG also for a
+ * candidate query outside [0, n_query) and for more edges in the rows than n_edges.  Ends with a
+ * full traversal, as pu_place_prescore. */
+int pu_place_refine(pu_ctx *ctx, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
+                    const uint8_t *query_codes, const int32_t *site_pattern,
+                    const double *site_weight, int n_codes, const double *code_table, double l0,
+                    double tol, int max_iter, int n_edges, const int64_t *cand_off,
+                    const int32_t *cand_query, double *pendant_out, double *lnl_out,
+                    double *derivs_out, int32_t *iters_out);
+/* HIP-event times (ms) of the last k_place_table, k_place_prescore and k_place_newton launches
+ * made while pu_ctx_profile was on. */
+int pu_place_kernel_ms(pu_ctx *ctx, double *table_ms, double *prescore_ms, double *newton_ms);
 /* Current lengths in pu_set_schedule's layout: brlens_out[n_ops][2], root length. */
 int pu_get_branch_lengths(pu_ctx *ctx, double *brlens_out, double *root_len_out);
 

@@ -88,6 +88,7 @@ struct TipStore {
 };
 
 struct SimState;  // pu_simulate.hip: the simulator's device buffers of a context
+struct PlaceState;  // pu_place.hip: the placement tables of a context
 
 }  // namespace pu
 
@@ -245,6 +246,8 @@ struct pu_ctx {
 
     // alignment simulation (pu_simulate.hip): allocated at the first pu_simulate* call
     pu::SimState *sim = nullptr;
+    // placement (pu_place.hip): allocated at the first pu_place_* call
+    pu::PlaceState *place = nullptr;
 
     // profiling: event triples per recorded run
     bool profile = false;
@@ -292,6 +295,8 @@ void edge_fill_args(const pu_ctx *c, EdgeArgs &a);
 int edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens);
 // pu_simulate.hip: release the simulator's buffers of a context
 void sim_free(pu_ctx *c);
+// pu_place.hip: release the placement buffers of a context
+void place_free(pu_ctx *c);
 // enqueue the ascertainment-bias correction of site_lnl and *lnl (no-op when off)
 int enqueue_ascbias(pu_ctx *c, double *lnl);
 // stateless seam calls (pu_clv, pu_lnl_node, pu_lnl_branch*): one scratch buffer and stream

@@ -1,0 +1,933 @@
+// pu_place.hip -- phylogenetic placement of query sequences on the device-resident CLVs of a
+// context (the reference has none): the gfx950 kernels that score and optimise a
+// query joined at the midpoint of an edge, and their C ABI (include/phylo_hip.h):
+//   pu_place_max_cat     the table kernel's category limit per alphabet (host only)
+//   pu_place_edge        all queries at one edge on the current partials
+//   pu_place_prescore    one pass of the optimising traversal: every query at every edge, at a
+//                        fixed pendant length
+//   pu_place_refine      the same pass: the pendant length of chosen (edge, query) pairs
+//                        optimised in the kernel
+//   pu_place_kernel_ms   the kernel times of the last launches under pu_ctx_profile
+//
+// While the optimising traversal stands on edge (n, o) of length t, partials[n] holds the
+// subtree below n and partials[o], re-oriented, everything else (pu_ancestral.hip).  A query
+// joined at the midpoint is a third vector meeting those two at a new node.  With A, B the two
+// vectors of (pattern p, category c), sA, sB their log scalers, z the query's tip vector (a row
+// of its code table) and l its pendant length:
+//   a_pc(i)   = pi_i [P_c(t/2) A_pc](i) [P_c(t/2) B_pc](i)
+//   sigma_pc  = sA_pc + sB_pc,  m_p = max_c sigma_pc  (over the categories with sum_i a_pc > 0)
+//   f_pc(l,z) = sum_i a_pc(i) [P_c(l) z](i) = sum_k T_pc(k) e^{lambda_k r_c l} u_k(z)
+//               T_pc = V^T a_pc,  u(z) = V^-1 z
+//   F_p(l,z)  = sum_c w_c e^{sigma_pc - m_p} f_pc(l,z)
+//   lnL(q,l)  = sum_s sw_s (m_p(s) + log F_p(s)(l, z_qs))
+// p(s) the pattern of the query's column s, sw its weight.  The kernels only read the context.
+//
+// k_place_table (k_ancestral's mapping: a workgroup is one 64-pattern tile, a lane a pattern,
+// wave w owns categories w, w + nw, ...) writes, per pattern, the pre-mixed eigen-basis table
+// W_pc(k) = w_c e^{sigma_pc - m_p} T_pc(k) as [p][c][k], m_p and -- for a pendant length l0 --
+// the log table G[p][code] = m_p + log sum_c sum_k W_pc(k) e^{lambda_k r_c l0} u_k(code).
+// k_place_prescore adds sw_s G[p(s)][code_qs] over fixed chunks of kPlaceChunk sites, one
+// workgroup per (query, chunk), and k_place_chunk_sum adds a query's chunks in ascending order.
+// k_place_newton runs pu_edge.cpp's newton() for one query per workgroup on W.  Every sum runs
+// in a fixed order and nothing written is read by another workgroup of the same launch: two
+// runs are bitwise equal, and a query's numbers do not depend on the other queries.
+#include <math.h>
+
+#include <cmath>
+#include <vector>
+
+#include "pu_ctx.h"
+#include "pu_edge_dev.h"
+
+using namespace pu;
+
+namespace {
+
+constexpr int kMaxCodes = 32;      // rows of a query code table
+constexpr int kPlaceMaxWaves = 8;  // k_place_table
+constexpr int kPlaceChunk = 2048;  // sites per k_place_prescore workgroup: a constant, so that a
+                                   // query's sum order depends on nothing else
+constexpr int kPlaceThreads = 256;  // k_place_prescore, k_place_chunk_sum
+// k_place_newton: 16 waves on one candidate.  A walk over many edges launches few candidates per
+// edge, each workgroup alone on its CU and bound by the latency of its strided reads of W: the
+// refine pass of 5000 candidates over 97 edges (cfg2) took 770 ms with 4 waves
+constexpr int kNewtonThreads = 1024;
+constexpr int kPlaceMaxCK = 256;    // C * K of any context the table kernel takes (64 x 4)
+constexpr double kMinLen = 1e-8;    // pu_edge.cpp kMinLen / kMaxLen
+constexpr double kMaxLen = 100.0;
+constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
+constexpr int kCtxMaxCat = 64;            // pu_ctx_create takes no more categories
+
+__host__ __device__ inline int place_waves(int C) {
+    return C < kPlaceMaxWaves ? C : kPlaceMaxWaves;
+}
+
+struct TableArgs {
+    NodeSrc n, o;     // the two ends of the edge
+    double half;      // t / 2
+    double l0;        // the pendant length of G
+    int n_codes;
+    const double *u;  // [n_codes][K] u(code) = V^-1 table[code]
+    double *W;        // [S][C][K]
+    double *m;        // [S]
+    double *G;        // [S][n_codes] (nullptr: not written)
+};
+
+// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][u 32*K]
+// [e^{lambda r t/2} C*K][e^{lambda r l0} C*K][P C*K*K][m 64][per (category, pattern): a / T / W
+// (0..K-1), sum_i a, sigma -- later the mix weight: C*(K+2)*64]
+struct PlaceLds {
+    size_t evecs, ivecs, evals, pi, rates, u, ex, ex0, P, mx, vals, total;
+    __host__ __device__ PlaceLds(int K, int C) {
+        evecs = 0;
+        ivecs = evecs + (size_t)K * K;
+        evals = ivecs + (size_t)K * K;
+        pi = evals + K;
+        rates = pi + K;
+        u = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+        ex = u + (size_t)kMaxCodes * K;
+        ex0 = ex + (size_t)C * K;
+        P = ex0 + (size_t)C * K;
+        mx = P + (size_t)C * K * K;
+        vals = mx + kLanes;
+        total = vals + (size_t)C * (K + 2) * kLanes;
+    }
+};
+
+template <int K>
+__global__ void __launch_bounds__(64 * kPlaceMaxWaves) k_place_table(EdgeArgs a, TableArgs q) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int C = a.C;
+    const PlaceLds L(K, C);
+    const int tile = blockIdx.x, l = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int64_t site = (int64_t)tile * kLanes + l;
+    const int64_t site_c = site < a.S ? site : a.S - 1;
+    const bool live = site < a.S;
+    const double *ev = lds + L.evecs, *iv = lds + L.ivecs, *el = lds + L.evals,
+                 *pi = lds + L.pi, *rt = lds + L.rates, *ex = lds + L.ex, *ex0 = lds + L.ex0,
+                 *P = lds + L.P, *u = lds + L.u;
+    double *vals = lds + L.vals, *mx = lds + L.mx;
+    constexpr int kRow = (K + 2) * kLanes;  // doubles per category in vals
+
+    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
+        lds[L.evecs + i] = a.evecs[i];
+        lds[L.ivecs + i] = a.ivecs[i];
+    }
+    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+        lds[L.evals + i] = a.evals[i];
+        lds[L.pi + i] = a.pi[i];
+    }
+    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    for (int i = threadIdx.x; i < q.n_codes * K; i += blockDim.x) lds[L.u + i] = q.u[i];
+    __syncthreads();
+    // P_c(t/2) = evecs diag(e^{lambda (t/2 r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
+    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
+        const int k = idx % K, c = idx / K;
+        lds[L.ex + idx] = exp(el[k] * (q.half * rt[c]));
+        lds[L.ex0 + idx] = exp(el[k] * (q.l0 * rt[c]));
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
+        const int ij = idx % (K * K), c = idx / (K * K);
+        const int i = ij / K, j = ij - i * K;
+        const double *e = ex + c * K;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
+        lds[L.P + idx] = acc;
+    }
+    __syncthreads();
+
+    // K = 20: the state loops stay rolled over the rows (k_ancestral's way: the rows of P and V
+    // are read from LDS where they are used, a_i waits in the lane's own LDS column)
+    constexpr int kRowUnroll = K > 4 ? 1 : K;
+    for (int c = w; c < C; c += nw) {
+        double A[K], B[K], sA, sB;
+        node_vec<K>(a, q.n, c, tile, l, site_c, A, sA);
+        node_vec<K>(a, q.o, c, tile, l, site_c, B, sB);
+        const double *Pc = P + (size_t)c * K * K;
+        double *g = vals + (size_t)c * kRow + l;
+        double asum = 0.0;
+#pragma unroll kRowUnroll
+        for (int i = 0; i < K; ++i) {
+            double ya = 0.0, yb = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                ya = fma(Pc[i * K + j], A[j], ya);
+                yb = fma(Pc[i * K + j], B[j], yb);
+            }
+            const double ai = (pi[i] * ya) * yb;
+            g[i * kLanes] = ai;
+            asum += ai;
+        }
+        // T = V^T a: row i of V against a_i, the K sums in registers
+        double T[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) T[k] = 0.0;
+#pragma unroll kRowUnroll
+        for (int i = 0; i < K; ++i) {
+            const double ai = g[i * kLanes];
+#pragma unroll
+            for (int k = 0; k < K; ++k) T[k] = fma(ev[i * K + k], ai, T[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) g[k * kLanes] = T[k];
+        g[K * kLanes] = asum;
+        g[(K + 1) * kLanes] = sA + sB;
+    }
+    __syncthreads();
+    if (w == 0) {
+        // wave 0 mixes the categories of its 64 patterns.  Only categories with sum_i a > 0
+        // take part (k_edge's rule: an all-zero vector keeps an unrescaled scaler, which must
+        // not set m); the mix weight w_c e^{sigma_c - m} replaces sigma_c
+        double *vs = vals + l;
+        double m = -INFINITY;
+        for (int c = 0; c < C; ++c)
+            if (vs[(size_t)c * kRow + K * kLanes] > 0.0)
+                m = fmax(m, vs[(size_t)c * kRow + (K + 1) * kLanes]);
+        for (int c = 0; c < C; ++c) {
+            double we = 0.0;
+            if (vs[(size_t)c * kRow + K * kLanes] > 0.0) {
+                const double sc = vs[(size_t)c * kRow + (K + 1) * kLanes];
+                we = a.weights[c] * (sc == m ? 1.0 : exp(sc - m));
+            }
+            vs[(size_t)c * kRow + (K + 1) * kLanes] = we;
+        }
+        mx[l] = m;
+        if (live) q.m[site] = m;
+    }
+    __syncthreads();
+    // W = mix weight x T, kept in LDS for G and written [p][c][k]: a lane's C*K values are one
+    // contiguous run
+    constexpr int kPairUnroll = K > 4 ? 2 : K / 2;
+    for (int c = w; c < C; c += nw) {
+        double *g = vals + (size_t)c * kRow + l;
+        const double we = g[(K + 1) * kLanes];
+        dbl2 *dst = reinterpret_cast<dbl2 *>(q.W + ((size_t)site_c * C + c) * K);
+#pragma unroll kPairUnroll
+        for (int kp = 0; kp < K / 2; ++kp) {
+            const double w0 = we * g[(2 * kp) * kLanes], w1 = we * g[(2 * kp + 1) * kLanes];
+            g[(2 * kp) * kLanes] = w0;
+            g[(2 * kp + 1) * kLanes] = w1;
+            if (live) dst[kp] = dbl2{w0, w1};
+        }
+    }
+    if (!q.G) return;
+    __syncthreads();
+    // H(k) = sum_c W_c(k) e^{lambda_k r_c l0}, by every wave for its own lanes; then the codes
+    // are dealt to the waves: G[p][code] = m + log sum_k H(k) u_k(code)
+    double H[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) H[k] = 0.0;
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        const double *g = vals + (size_t)c * kRow + l, *e = ex0 + c * K;
+#pragma unroll
+        for (int k = 0; k < K; ++k) H[k] = fma(g[k * kLanes], e[k], H[k]);
+    }
+    const double m = mx[l];
+#pragma unroll 1
+    for (int code = w; code < q.n_codes; code += nw) {
+        const double *uz = u + code * K;
+        double F = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) F = fma(H[k], uz[k], F);
+        if (live) q.G[(size_t)site * q.n_codes + code] = F > 0.0 ? m + log(F) : -INFINITY;
+    }
+}
+
+// the queries of a call on the device
+struct QueryDev {
+    const uint8_t *codes;  // [Q][n_sites]
+    const int32_t *map;    // [n_sites] p(s) (nullptr: the identity)
+    const double *sw;      // [n_sites] (nullptr: 1)
+    int64_t n_sites;
+    int n_codes, n_chunks;
+};
+
+// part[q][chunk] = sum over the chunk's sites of sw_s G[p(s)][code_qs]: a thread adds its 8
+// sites in ascending order, then a fixed 64-lane tree, then the four waves in order
+__global__ void __launch_bounds__(kPlaceThreads) k_place_prescore(QueryDev d, int n_query,
+                                                                  const double *__restrict__ G,
+                                                                  double *__restrict__ part) {
+    __shared__ double red[kPlaceThreads / 64];
+    const int64_t blk = blockIdx.x;
+    const int64_t qi = blk / d.n_chunks, chunk = blk - qi * d.n_chunks;
+    if (qi >= n_query) return;
+    const uint8_t *codes = d.codes + (size_t)qi * d.n_sites;
+    const int64_t base = chunk * kPlaceChunk;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kPlaceChunk / kPlaceThreads; ++j) {
+        const int64_t s = base + j * kPlaceThreads + threadIdx.x;
+        if (s < d.n_sites) {
+            const double wgt = d.sw ? d.sw[s] : 1.0;
+            if (wgt != 0.0) {
+                const int64_t p = d.map ? d.map[s] : s;
+                acc += wgt * G[(size_t)p * d.n_codes + codes[s]];
+            }
+        }
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = 0.0;
+        for (int k = 0; k < kPlaceThreads / 64; ++k) r += red[k];
+        part[blk] = r;
+    }
+}
+
+// second launch: a thread per query adds its chunks in ascending order
+__global__ void __launch_bounds__(kPlaceThreads) k_place_chunk_sum(const double *__restrict__ part,
+                                                                   int n_query, int n_chunks,
+                                                                   double *__restrict__ score) {
+    const int64_t qi = (int64_t)blockIdx.x * kPlaceThreads + threadIdx.x;
+    if (qi >= n_query) return;
+    double s = 0.0;
+    for (int k = 0; k < n_chunks; ++k) s += part[(size_t)qi * n_chunks + k];
+    score[qi] = s;
+}
+
+struct NewtonArgsP {
+    const int32_t *list;  // [n] the queries of this launch (nullptr: 0..n-1)
+    const double *W, *m, *u, *evals, *rates;
+    int C;
+    double l0, tol;
+    int max_iter;
+    double *out;  // [n][5]: l*, lnL(l*), dlnL/dl, d2lnL/dl2, steps
+};
+
+// One workgroup per query: pu_edge.cpp's newton() on the pendant length, every evaluation a
+// pass of the workgroup's 1024 threads over the query's sites.  Per evaluation e^{lambda_k r_c l}
+// and its factors (lambda_k r_c), (lambda_k r_c)^2 stand in LDS; a thread adds its sites in
+// ascending order, then a fixed 64-lane tree, then the sixteen waves in order.  Every thread takes
+// the same step from the same sums.
+template <int K>
+__global__ void __launch_bounds__(kNewtonThreads) k_place_newton(QueryDev d, NewtonArgsP n) {
+    __shared__ __attribute__((aligned(16))) double u[kMaxCodes * K];
+    __shared__ __attribute__((aligned(16))) double E[3][kPlaceMaxCK];
+    __shared__ double red[3][kNewtonThreads / 64];
+    constexpr int kPairUnroll = K > 4 ? 2 : K / 2;
+    const int C = n.C, CK = n.C * K;
+    const int64_t qi = n.list ? n.list[blockIdx.x] : blockIdx.x;
+    const uint8_t *codes = d.codes + (size_t)qi * d.n_sites;
+    for (int i = threadIdx.x; i < d.n_codes * K; i += blockDim.x) u[i] = n.u[i];
+
+    // {lnL, dlnL/dl, d2lnL/dl2} at pendant length t
+    auto eval = [&](double t, double (&r)[3]) {
+        __syncthreads();  // the last evaluation's readers of E and red are done (and u is set)
+        for (int idx = threadIdx.x; idx < CK; idx += blockDim.x) {
+            const double lam = n.evals[idx % K] * n.rates[idx / K];
+            const double e = exp(lam * t);
+            E[0][idx] = e;
+            E[1][idx] = e * lam;
+            E[2][idx] = e * (lam * lam);
+        }
+        __syncthreads();
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int64_t s = threadIdx.x; s < d.n_sites; s += kNewtonThreads) {
+            const double wgt = d.sw ? d.sw[s] : 1.0;
+            if (wgt == 0.0) continue;
+            const int64_t p = d.map ? d.map[s] : s;
+            const double *Wp = n.W + (size_t)p * CK;
+            const double *uz = u + (int)codes[s] * K;
+            double F = 0.0, F1 = 0.0, F2 = 0.0;
+#pragma unroll 1
+            for (int c = 0; c < C; ++c) {
+                const dbl2 *Wc = reinterpret_cast<const dbl2 *>(Wp + c * K);
+                const double *e0 = E[0] + c * K, *e1 = E[1] + c * K, *e2 = E[2] + c * K;
+#pragma unroll kPairUnroll
+                for (int kp = 0; kp < K / 2; ++kp) {
+                    const dbl2 wv = Wc[kp];
+                    const double x0 = wv.x * uz[2 * kp], x1 = wv.y * uz[2 * kp + 1];
+                    F = fma(x0, e0[2 * kp], F);
+                    F1 = fma(x0, e1[2 * kp], F1);
+                    F2 = fma(x0, e2[2 * kp], F2);
+                    F = fma(x1, e0[2 * kp + 1], F);
+                    F1 = fma(x1, e1[2 * kp + 1], F1);
+                    F2 = fma(x1, e2[2 * kp + 1], F2);
+                }
+            }
+            if (F > 0.0) {
+                const double g1 = F1 / F;
+                a0 += wgt * (n.m[p] + log(F));
+                a1 += wgt * g1;
+                a2 += wgt * (F2 / F - g1 * g1);
+            } else {
+                a0 = -INFINITY;  // a site of likelihood 0 and non-zero weight
+            }
+        }
+        a0 = wave_sum(a0);
+        a1 = wave_sum(a1);
+        a2 = wave_sum(a2);
+        if ((threadIdx.x & 63) == 0) {
+            red[0][threadIdx.x >> 6] = a0;
+            red[1][threadIdx.x >> 6] = a1;
+            red[2][threadIdx.x >> 6] = a2;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < kNewtonThreads / 64; ++k) s += red[j][k];
+            r[j] = s;
+        }
+    };
+
+    // pu_edge.cpp newton(): a step that lowers the lnL is halved (up to 30 times); a non-concave
+    // point moves by expansion (d1 > 0) or halving; lengths stay in [kMinLen, kMaxLen]
+    double t = fmin(fmax(n.l0, kMinLen), kMaxLen);
+    double r[3];
+    eval(t, r);
+    int it = 0;
+    for (; it < n.max_iter; ++it) {
+        const double lnl = r[0], d1 = r[1], d2 = r[2];
+        if (!isfinite(lnl)) break;
+        const double step = d2 < 0.0 ? -d1 / d2 : (d1 > 0.0 ? t + 0.1 : -0.5 * t);
+        double tn = fmin(fmax(t + step, kMinLen), kMaxLen);
+        if (tn == t) break;
+        double rn[3];
+        bool ok = false;
+        for (int h = 0; h < 30; ++h) {
+            eval(tn, rn);
+            if (rn[0] >= lnl - 1e-13 * fabs(lnl)) {
+                ok = true;
+                break;
+            }
+            tn = 0.5 * (t + tn);
+        }
+        if (!ok) break;  // no ascent along this direction: t is (numerically) optimal
+        const double dt = fabs(tn - t);
+        t = tn;
+        r[0] = rn[0];
+        r[1] = rn[1];
+        r[2] = rn[2];
+        if (dt <= n.tol * (1.0 + t)) {
+            ++it;
+            break;
+        }
+    }
+    if (threadIdx.x == 0) {
+        double *o = n.out + 5 * (size_t)blockIdx.x;
+        o[0] = t;
+        o[1] = r[0];
+        o[2] = r[1];
+        o[3] = r[2];
+        o[4] = (double)it;
+    }
+}
+
+size_t place_lds_bytes(int K, int C) { return PlaceLds(K, C).total * sizeof(double); }
+
+// the largest C whose tables fit the LDS of a CU and a context can hold
+int place_max_cat(int K) {
+    int C = 0;
+    while (C < kCtxMaxCat && (C + 1) * K <= kPlaceMaxCK && place_lds_bytes(K, C + 1) <= kLdsBytes)
+        ++C;
+    return C;
+}
+
+// a device buffer owned by one call
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf() { dfree(p); }
+    int alloc(std::string *err, size_t n) { return dalloc(err, &p, n); }
+};
+
+// a device buffer of the context that only grows
+template <class T>
+int grow(pu_ctx *c, T *&p, size_t &cap, size_t need) {
+    if (cap >= need) return PU_OK;
+    dfree(p);
+    cap = 0;
+    int rc = dalloc(&c->err, &p, need);
+    if (rc) return rc;
+    cap = need;
+    return PU_OK;
+}
+
+}  // namespace
+
+// the placement buffers of a context: the tables of the edge the walk stands on, the chunk
+// sums, and the HIP events of the last launches when profiling
+struct pu::PlaceState {
+    double *d_W = nullptr, *d_m = nullptr, *d_G = nullptr, *d_u = nullptr, *d_part = nullptr;
+    size_t W_cap = 0, m_cap = 0, G_cap = 0, u_cap = 0, part_cap = 0;
+    hipEvent_t ev[3][2] = {};
+    bool stamped[3] = {};  // a pair was recorded since the last stamp
+    float ms[3] = {};      // table, prescore, newton
+};
+
+void pu::place_free(pu_ctx *c) {
+    PlaceState *s = c->place;
+    if (!s) return;
+    dfree(s->d_W);
+    dfree(s->d_m);
+    dfree(s->d_G);
+    dfree(s->d_u);
+    dfree(s->d_part);
+    for (auto &pair : s->ev)
+        for (hipEvent_t &e : pair)
+            if (e) (void)hipEventDestroy(e);
+    delete s;
+    c->place = nullptr;
+}
+
+namespace {
+
+// what every call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
+// (pu_ancestral.hip's ancestral_ready)
+int place_ready(pu_ctx *c, const char *what) {
+    int rc = edge_prepare(c);
+    if (rc) return rc;
+    if (c->flags & PU_LNL_ONLY)
+        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
+                       "storage)", what);
+    if (c->host_p)
+        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
+                       "(pu_set_model); this context is on host transition matrices", what);
+    if (c->asc_mode)
+        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
+                       "implemented", what);
+    if (c->K != 2 && c->K != 4 && c->K != 20)
+        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
+    if (c->C > place_max_cat(c->K))
+        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
+                       "one workgroup (at most %d)", what, c->C, c->K, place_max_cat(c->K));
+    if (c->h_eig.size() != (size_t)(2 * c->K * c->K + c->K))
+        return set_err(&c->err, PU_E_STATE, "%s: no eigen-system in the context", what);
+    return PU_OK;
+}
+
+// the caller's queries: checked on the host, then uploaded once
+struct QueryHost {
+    int n_query;
+    int64_t n_sites;
+    const uint8_t *codes;
+    const int32_t *map;
+    const double *sw;
+    int n_codes;
+    const double *table;
+    double l0;
+};
+
+struct QuerySet {
+    DevBuf<uint8_t> codes;
+    DevBuf<int32_t> map;
+    DevBuf<double> sw;
+    QueryDev d = {};
+};
+
+int check_queries(pu_ctx *c, const char *fn, const QueryHost &h) {
+    if (!h.codes || !h.table)
+        return set_err(&c->err, PU_E_ARG, "%s: null query buffer", fn);
+    if (h.n_query < 1 || h.n_sites < 1)
+        return set_err(&c->err, PU_E_ARG, "%s: %d queries of %lld sites", fn, h.n_query,
+                       (long long)h.n_sites);
+    if (h.n_codes < 1 || h.n_codes > kMaxCodes)
+        return set_err(&c->err, PU_E_ARG, "%s: n_codes %d outside [1, %d]", fn, h.n_codes,
+                       kMaxCodes);
+    if (!std::isfinite(h.l0) || h.l0 <= 0.0)
+        return set_err(&c->err, PU_E_ARG, "%s: pendant length %g", fn, h.l0);
+    if (!h.map && h.n_sites != c->S)
+        return set_err(&c->err, PU_E_ARG, "%s: %lld sites on %lld patterns without a site map", fn,
+                       (long long)h.n_sites, (long long)c->S);
+    if (h.map)
+        for (int64_t s = 0; s < h.n_sites; ++s)
+            if (h.map[s] < 0 || h.map[s] >= c->S)
+                return set_err(&c->err, PU_E_ARG, "%s: site_pattern[%lld] = %d outside [0, %lld)",
+                               fn, (long long)s, h.map[s], (long long)c->S);
+    const size_t n = (size_t)h.n_query * h.n_sites;
+    for (size_t i = 0; i < n; ++i)
+        if (h.codes[i] >= h.n_codes)
+            return set_err(&c->err, PU_E_ARG, "%s: query %zu, site %zu: code %d of %d", fn,
+                           i / h.n_sites, i % h.n_sites, h.codes[i], h.n_codes);
+    return PU_OK;
+}
+
+// the queries and u(code) = V^-1 table[code] to the device; the context's buffers sized for
+// them (with_G: the log table and the chunk sums of the pre-score)
+int upload_queries(pu_ctx *c, const QueryHost &h, bool with_G, QuerySet &qs) {
+    if (!c->place) c->place = new PlaceState();
+    PlaceState *s = c->place;
+    const int K = c->K;
+    const size_t S = (size_t)c->S, n = (size_t)h.n_query * h.n_sites;
+    const int n_chunks = (int)((h.n_sites + kPlaceChunk - 1) / kPlaceChunk);
+    int rc;
+    if ((rc = qs.codes.alloc(&c->err, n)) ||
+        (rc = qs.map.alloc(&c->err, h.map ? (size_t)h.n_sites : 0)) ||
+        (rc = qs.sw.alloc(&c->err, h.sw ? (size_t)h.n_sites : 0)) ||
+        (rc = grow(c, s->d_W, s->W_cap, S * c->C * K)) || (rc = grow(c, s->d_m, s->m_cap, S)) ||
+        (rc = grow(c, s->d_u, s->u_cap, (size_t)kMaxCodes * K)))
+        return rc;
+    if (with_G && ((rc = grow(c, s->d_G, s->G_cap, S * kMaxCodes)) ||
+                   (rc = grow(c, s->d_part, s->part_cap, (size_t)h.n_query * n_chunks))))
+        return rc;
+    std::vector<double> u((size_t)h.n_codes * K);
+    const double *iv = c->h_eig.data() + (size_t)K * K + K;
+    for (int code = 0; code < h.n_codes; ++code)
+        for (int k = 0; k < K; ++k) {
+            double acc = 0.0;
+            for (int j = 0; j < K; ++j) acc += iv[k * K + j] * h.table[(size_t)code * K + j];
+            u[(size_t)code * K + k] = acc;
+        }
+    HIPCHK(&c->err, hipMemcpyAsync(qs.codes.p, h.codes, n, hipMemcpyHostToDevice, c->stream));
+    if (h.map)
+        HIPCHK(&c->err, hipMemcpyAsync(qs.map.p, h.map, (size_t)h.n_sites * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, c->stream));
+    if (h.sw)
+        HIPCHK(&c->err, hipMemcpyAsync(qs.sw.p, h.sw, (size_t)h.n_sites * sizeof(double),
+                                       hipMemcpyHostToDevice, c->stream));
+    HIPCHK(&c->err, hipMemcpyAsync(s->d_u, u.data(), u.size() * sizeof(double),
+                                   hipMemcpyHostToDevice, c->stream));
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));  // u leaves scope
+    qs.d.codes = qs.codes.p;
+    qs.d.map = qs.map.p;
+    qs.d.sw = qs.sw.p;
+    qs.d.n_sites = h.n_sites;
+    qs.d.n_codes = h.n_codes;
+    qs.d.n_chunks = n_chunks;
+    return PU_OK;
+}
+
+// HIP events around launch `which` (0 table, 1 prescore, 2 newton) while profiling
+int mark(pu_ctx *c, int which, int end) {
+    if (!c->profile) return PU_OK;
+    PlaceState *s = c->place;
+    hipEvent_t &e = s->ev[which][end];
+    if (!e) HIPCHK(&c->err, hipEventCreate(&e));
+    HIPCHK(&c->err, hipEventRecord(e, c->stream));
+    if (end) s->stamped[which] = true;
+    return PU_OK;
+}
+
+// after the stream has drained: the times of the last launches made while profiling
+int place_stamp(pu_ctx *c) {
+    PlaceState *s = c->place;
+    if (!c->profile || !s) return PU_OK;
+    for (int k = 0; k < 3; ++k)
+        if (s->stamped[k]) {
+            HIPCHK(&c->err, hipEventElapsedTime(&s->ms[k], s->ev[k][0], s->ev[k][1]));
+            s->stamped[k] = false;
+        }
+    return PU_OK;
+}
+
+template <int K>
+void launch_table_k(hipStream_t st, const EdgeArgs &a, const TableArgs &q) {
+    const dim3 grid((unsigned)a.n_tiles), block(64 * place_waves(a.C));
+    hipLaunchKernelGGL(k_place_table<K>, grid, block, place_lds_bytes(K, a.C), st, a, q);
+}
+
+// k_place_table of edge (n, o) at length t, queued on the context's stream
+int table_enqueue(pu_ctx *c, NodeSrc n, NodeSrc o, double t, const QueryHost &h, bool with_G) {
+    PlaceState *s = c->place;
+    EdgeArgs a;
+    edge_fill_args(c, a);
+    TableArgs q = {};
+    q.n = n;
+    q.o = o;
+    q.half = 0.5 * t;
+    q.l0 = h.l0;
+    q.n_codes = h.n_codes;
+    q.u = s->d_u;
+    q.W = s->d_W;
+    q.m = s->d_m;
+    q.G = with_G ? s->d_G : nullptr;
+    int rc;
+    if ((rc = mark(c, 0, 0))) return rc;
+    switch (c->K) {
+        case 2: launch_table_k<2>(c->stream, a, q); break;
+        case 4: launch_table_k<4>(c->stream, a, q); break;
+        default: launch_table_k<20>(c->stream, a, q); break;
+    }
+    HIPCHK(&c->err, hipGetLastError());
+    return mark(c, 0, 1);
+}
+
+// the pre-score of all queries on the tables in place: score_dev[Q]
+int prescore_enqueue(pu_ctx *c, const QuerySet &qs, int n_query, double *score_dev) {
+    PlaceState *s = c->place;
+    const int64_t blocks = (int64_t)n_query * qs.d.n_chunks;
+    if (blocks > 0x7fffffffLL)
+        return set_err(&c->err, PU_E_ARG, "placement: %d queries x %d chunks exceed one launch",
+                       n_query, qs.d.n_chunks);
+    int rc;
+    if ((rc = mark(c, 1, 0))) return rc;
+    hipLaunchKernelGGL(k_place_prescore, dim3((unsigned)blocks), dim3(kPlaceThreads), 0, c->stream,
+                       qs.d, n_query, s->d_G, s->d_part);
+    HIPCHK(&c->err, hipGetLastError());
+    if ((rc = mark(c, 1, 1))) return rc;
+    hipLaunchKernelGGL(k_place_chunk_sum, dim3((unsigned)((n_query + kPlaceThreads - 1) /
+                                                          kPlaceThreads)),
+                       dim3(kPlaceThreads), 0, c->stream, s->d_part, n_query, qs.d.n_chunks,
+                       score_dev);
+    HIPCHK(&c->err, hipGetLastError());
+    return PU_OK;
+}
+
+// k_place_newton for n queries (list_dev, nullptr: 0..n-1) on the tables in place: out_dev[n][5]
+int newton_enqueue(pu_ctx *c, const QuerySet &qs, const int32_t *list_dev, int n, double l0,
+                   double tol, int max_iter, double *out_dev) {
+    PlaceState *s = c->place;
+    NewtonArgsP a = {};
+    a.list = list_dev;
+    a.W = s->d_W;
+    a.m = s->d_m;
+    a.u = s->d_u;
+    a.evals = c->d_evals;
+    a.rates = c->d_rates;
+    a.C = c->C;
+    a.l0 = l0;
+    a.tol = tol;
+    a.max_iter = max_iter;
+    a.out = out_dev;
+    int rc;
+    if ((rc = mark(c, 2, 0))) return rc;
+    const dim3 grid((unsigned)n), block(kNewtonThreads);
+    switch (c->K) {
+        case 2: hipLaunchKernelGGL(k_place_newton<2>, grid, block, 0, c->stream, qs.d, a); break;
+        case 4: hipLaunchKernelGGL(k_place_newton<4>, grid, block, 0, c->stream, qs.d, a); break;
+        default: hipLaunchKernelGGL(k_place_newton<20>, grid, block, 0, c->stream, qs.d, a); break;
+    }
+    HIPCHK(&c->err, hipGetLastError());
+    return mark(c, 2, 1);
+}
+
+template <class T>
+int to_host(pu_ctx *c, T *dst, const T *src, size_t n) {
+    if (n) HIPCHK(&c->err, hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return PU_OK;
+}
+
+// one re-orientation / restore row of the optimising traversal, as pu_optimise_sweep applies it
+int apply_row(pu_ctx *c, const int32_t *row) {
+    if (row[0] < 0) return PU_OK;
+    int k1, k2, rc;
+    if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
+        return rc;
+    const double bl[2] = {c->up_len[k1], c->up_len[k2]};
+    return edge_update_ops(c, 1, row, bl);
+}
+
+// An error in mid-walk leaves nodes re-oriented towards the edge the walk stood on: one
+// traversal writes the post-order partials, the lnL and the sitewise lnL back, as the end of a
+// complete walk does (bad rows are refused here; a failed launch may fail the traversal too).
+// The first error is the one reported.
+int abandon_walk(pu_ctx *c, int rc) {
+    const std::string msg = c->err;
+    double lnl;
+    (void)pu_run(c, &lnl, nullptr);
+    return set_err(&c->err, rc, "%s", msg.c_str());
+}
+
+}  // namespace
+
+extern "C" {
+
+int pu_place_max_cat(int n_states) {
+    if (n_states != 2 && n_states != 4 && n_states != 20)
+        return set_err(nullptr, PU_E_ARG, "pu_place_max_cat: K=%d is not supported", n_states);
+    return place_max_cat(n_states);
+}
+
+int pu_place_edge(pu_ctx *c, int node, int other, double length, int n_query, int64_t n_sites,
+                  const uint8_t *query_codes, const int32_t *site_pattern,
+                  const double *site_weight, int n_codes, const double *code_table, double l0,
+                  double tol, int max_iter, double *score_out, double *pendant_out,
+                  double *lnl_out, double *derivs_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (!score_out || !pendant_out || !lnl_out || !derivs_out)
+        return set_err(&c->err, PU_E_ARG, "pu_place_edge: null buffer");
+    const QueryHost h = {n_query, n_sites, query_codes, site_pattern, site_weight,
+                         n_codes, code_table, l0};
+    int rc = place_ready(c, "placement");  // the context's state first: S below is then final
+    if (rc || (rc = check_queries(c, "pu_place_edge", h))) return rc;
+    if (!std::isfinite(length) || length <= 0.0)
+        return set_err(&c->err, PU_E_ARG, "pu_place_edge: length %g", length);
+    if (max_iter < 0 || !(tol >= 0.0))
+        return set_err(&c->err, PU_E_ARG, "pu_place_edge: tol %g, max_iter %d", tol, max_iter);
+    DeviceGuard g(c->device);
+    int key;
+    NodeSrc sn, so;
+    if ((rc = edge_key(c, node, other, &key)) || (rc = edge_node_src(c, node, &sn)) ||
+        (rc = edge_node_src(c, other, &so)))
+        return rc;
+    QuerySet qs;
+    if ((rc = upload_queries(c, h, true, qs))) return rc;
+    const size_t Q = (size_t)n_query;
+    DevBuf<double> d_score, d_nt;
+    if ((rc = d_score.alloc(&c->err, Q)) || (rc = d_nt.alloc(&c->err, max_iter ? 5 * Q : 0)))
+        return rc;
+    if ((rc = table_enqueue(c, sn, so, length, h, true)) ||
+        (rc = prescore_enqueue(c, qs, n_query, d_score.p)))
+        return rc;
+    if (max_iter && (rc = newton_enqueue(c, qs, nullptr, n_query, l0, tol, max_iter, d_nt.p)))
+        return rc;
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if ((rc = place_stamp(c)) || (rc = to_host(c, score_out, d_score.p, Q))) return rc;
+    if (!max_iter) {  // the pre-score alone
+        for (size_t i = 0; i < Q; ++i) {
+            pendant_out[i] = l0;
+            lnl_out[i] = score_out[i];
+            derivs_out[2 * i] = derivs_out[2 * i + 1] = NAN;
+        }
+        return PU_OK;
+    }
+    std::vector<double> nt(5 * Q);
+    if ((rc = to_host(c, nt.data(), d_nt.p, 5 * Q))) return rc;
+    for (size_t i = 0; i < Q; ++i) {
+        pendant_out[i] = nt[5 * i];
+        lnl_out[i] = nt[5 * i + 1];
+        derivs_out[2 * i] = nt[5 * i + 2];
+        derivs_out[2 * i + 1] = nt[5 * i + 3];
+    }
+    return PU_OK;
+}
+
+int pu_place_prescore(pu_ctx *c, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
+                      const uint8_t *query_codes, const int32_t *site_pattern,
+                      const double *site_weight, int n_codes, const double *code_table, double l0,
+                      int32_t *edges_out, double *lengths_out, double *score_out,
+                      int *n_edges_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (n_rows < 1 || !rows || !edges_out || !lengths_out || !score_out || !n_edges_out)
+        return set_err(&c->err, PU_E_ARG, "pu_place_prescore: no rows or a null buffer");
+    const QueryHost h = {n_query, n_sites, query_codes, site_pattern, site_weight,
+                         n_codes, code_table, l0};
+    int rc = place_ready(c, "placement");
+    if (rc || (rc = check_queries(c, "pu_place_prescore", h))) return rc;
+    const int cap = 2 * c->n_tips - 3;
+    int n_edges = 0;
+    for (int r = 0; r < n_rows; ++r) n_edges += rows[5 * (size_t)r + 3] >= 0;
+    if (n_edges > cap)
+        return set_err(&c->err, PU_E_ARG, "pu_place_prescore: more than 2 n_tips - 3 = %d edges "
+                       "in the rows", cap);
+    DeviceGuard g(c->device);
+    QuerySet qs;
+    if ((rc = upload_queries(c, h, true, qs))) return rc;
+    const size_t Q = (size_t)n_query;
+    // the scores of all edges stay on the device until the walk is over
+    DevBuf<double> d_score;
+    if ((rc = d_score.alloc(&c->err, (size_t)n_edges * Q))) return rc;
+    int count = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const int32_t *row = rows + 5 * (size_t)r;
+        if ((rc = apply_row(c, row))) return abandon_walk(c, rc);
+        if (row[3] < 0) continue;
+        const int nod = row[3], par = row[4];
+        int key;
+        NodeSrc sn, so;
+        if ((rc = edge_key(c, nod, par, &key)) || (rc = edge_node_src(c, nod, &sn)) ||
+            (rc = edge_node_src(c, par, &so)))
+            return abandon_walk(c, rc);
+        const double t = c->up_len[key];
+        if ((rc = table_enqueue(c, sn, so, t, h, true)) ||
+            (rc = prescore_enqueue(c, qs, n_query, d_score.p + count * Q)))
+            return abandon_walk(c, rc);
+        edges_out[2 * count] = nod;
+        edges_out[2 * count + 1] = par;
+        lengths_out[count] = t;
+        ++count;
+    }
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    if ((rc = place_stamp(c)) || (rc = to_host(c, score_out, d_score.p, count * Q))) return rc;
+    *n_edges_out = count;
+    // every node is back in its post-order orientation by the restore rows' updates; one
+    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
+    double lnl;
+    return pu_run(c, &lnl, nullptr);
+}
+
+int pu_place_refine(pu_ctx *c, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
+                    const uint8_t *query_codes, const int32_t *site_pattern,
+                    const double *site_weight, int n_codes, const double *code_table, double l0,
+                    double tol, int max_iter, int n_edges, const int64_t *cand_off,
+                    const int32_t *cand_query, double *pendant_out, double *lnl_out,
+                    double *derivs_out, int32_t *iters_out) {
+    if (!c) return set_err(nullptr, PU_E_ARG, "null context");
+    if (n_rows < 1 || !rows || !cand_off || !pendant_out || !lnl_out || !derivs_out || !iters_out)
+        return set_err(&c->err, PU_E_ARG, "pu_place_refine: no rows or a null buffer");
+    const QueryHost h = {n_query, n_sites, query_codes, site_pattern, site_weight,
+                         n_codes, code_table, l0};
+    int rc = place_ready(c, "placement");
+    if (rc || (rc = check_queries(c, "pu_place_refine", h))) return rc;
+    if (max_iter < 0 || !(tol >= 0.0))
+        return set_err(&c->err, PU_E_ARG, "pu_place_refine: tol %g, max_iter %d", tol, max_iter);
+    if (n_edges < 0 || cand_off[0] != 0)
+        return set_err(&c->err, PU_E_ARG, "pu_place_refine: n_edges %d, cand_off[0] %lld", n_edges,
+                       n_edges < 0 ? 0LL : (long long)cand_off[0]);
+    for (int e = 0; e < n_edges; ++e)
+        if (cand_off[e + 1] < cand_off[e] || cand_off[e + 1] - cand_off[e] > 0x7fffffffLL)
+            return set_err(&c->err, PU_E_ARG, "pu_place_refine: cand_off decreases at edge %d", e);
+    const size_t n_cand = (size_t)cand_off[n_edges];
+    if (n_cand && !cand_query)
+        return set_err(&c->err, PU_E_ARG, "pu_place_refine: null candidate list");
+    for (size_t i = 0; i < n_cand; ++i)
+        if (cand_query[i] < 0 || cand_query[i] >= n_query)
+            return set_err(&c->err, PU_E_ARG, "pu_place_refine: candidate %zu names query %d of "
+                           "%d", i, cand_query[i], n_query);
+    int walk_edges = 0;
+    for (int r = 0; r < n_rows; ++r) walk_edges += rows[5 * (size_t)r + 3] >= 0;
+    if (walk_edges > n_edges)
+        return set_err(&c->err, PU_E_ARG, "pu_place_refine: %d edges in the rows, cand_off holds "
+                       "%d", walk_edges, n_edges);
+    DeviceGuard g(c->device);
+    QuerySet qs;
+    if ((rc = upload_queries(c, h, false, qs))) return rc;
+    DevBuf<int32_t> d_list;
+    DevBuf<double> d_nt;
+    if ((rc = d_list.alloc(&c->err, n_cand)) || (rc = d_nt.alloc(&c->err, 5 * n_cand))) return rc;
+    if (n_cand) {
+        HIPCHK(&c->err, hipMemcpyAsync(d_list.p, cand_query, n_cand * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, c->stream));
+        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    }
+    int count = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        const int32_t *row = rows + 5 * (size_t)r;
+        if ((rc = apply_row(c, row))) return abandon_walk(c, rc);
+        if (row[3] < 0) continue;
+        const int64_t lo = cand_off[count], n = cand_off[count + 1] - lo;
+        ++count;
+        if (n == 0) continue;
+        int key;
+        NodeSrc sn, so;
+        if ((rc = edge_key(c, row[3], row[4], &key)) || (rc = edge_node_src(c, row[3], &sn)) ||
+            (rc = edge_node_src(c, row[4], &so)))
+            return abandon_walk(c, rc);
+        if ((rc = table_enqueue(c, sn, so, c->up_len[key], h, false)) ||
+            (rc = newton_enqueue(c, qs, d_list.p + lo, (int)n, l0, tol, max_iter,
+                                 d_nt.p + 5 * lo)))
+            return abandon_walk(c, rc);
+    }
+    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
+    std::vector<double> nt(5 * n_cand);
+    if ((rc = place_stamp(c)) || (rc = to_host(c, nt.data(), d_nt.p, 5 * n_cand))) return rc;
+    // candidates of edges past the walk's last keep NaN
+    for (size_t i = 0; i < n_cand; ++i) {
+        const bool done = i < (size_t)cand_off[count];
+        pendant_out[i] = done ? nt[5 * i] : NAN;
+        lnl_out[i] = done ? nt[5 * i + 1] : NAN;
+        derivs_out[2 * i] = done ? nt[5 * i + 2] : NAN;
+        derivs_out[2 * i + 1] = done ? nt[5 * i + 3] : NAN;
+        iters_out[i] = done ? (int32_t)nt[5 * i + 4] : -1;
+    }
+    double lnl;
+    return pu_run(c, &lnl, nullptr);
+}
+
+int pu_place_kernel_ms(pu_ctx *c, double *table_ms, double *prescore_ms, double *newton_ms) {
+    if (!c || !table_ms || !prescore_ms || !newton_ms)
+        return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
+    const PlaceState *s = c->place;
+    *table_ms = s ? (double)s->ms[0] : 0.0;
+    *prescore_ms = s ? (double)s->ms[1] : 0.0;
+    *newton_ms = s ? (double)s->ms[2] : 0.0;
+    return PU_OK;
+}
+
+}  // extern "C"

@@ -52,7 +52,14 @@ parameter of the ``-m`` model (``rates``, ``kappa``, ``alpha_y``, ``alpha_r``, `
 ``alpha``) -- jointly with all branch lengths on the exact gradient
 (``phylo_utils_amd.modelfit``), prints one extra line ``model = <string>`` before ``lnL = ``, the
 fitted model in the grammar above (``%.10g``) so that ``-m`` reads it back, and writes the tree
-with the fitted lengths to ``-o``.
+with the fitted lengths to ``-o``;
+``--place QUERIES.fasta [--keep K] --jplace OUT.jplace`` (after ``-t`` or ``--nj``, and after
+``--nni`` / ``--fit`` when given) places the query sequences of QUERIES.fasta -- aligned to ``-s``,
+of its full length -- on the final tree without rebuilding it (``phylo_utils_amd.place``): every
+query is scored at every edge, its K best edges (default 5) are refined on the pendant length,
+and OUT.jplace receives them in jplace version 3 (``edge_num, likelihood, like_weight_ratio,
+distal_length, pendant_length``); ``--placed-trees FILE`` receives one Newick per query, the tree
+with that query joined at its best placement (``-o`` stays what the other options make it).
 """
 from __future__ import annotations
 
@@ -194,6 +201,16 @@ def parse_cli(argv=None):
                          "free parameter of the -m model) jointly with all branch lengths, "
                          "after --optimise / --nni; prints a 'model = ' line that -m reads back; "
                          "-o receives the Newick with the fitted lengths")
+    ap.add_argument("--place", type=str, default=None, metavar="QUERIES",
+                    help="place the aligned query sequences of this FASTA file on the final tree "
+                         "(needs --jplace)")
+    ap.add_argument("--keep", type=int, default=5, metavar="K",
+                    help="with --place: edges per query whose pendant length is refined")
+    ap.add_argument("--jplace", type=str, default=None, metavar="FILE",
+                    help="with --place: the jplace (version 3) file to write")
+    ap.add_argument("--placed-trees", type=str, default=None, metavar="FILE", dest="placed_trees",
+                    help="with --place: write one Newick per query, the tree with the query "
+                         "joined at its best placement")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -205,6 +222,18 @@ def validate_args(args):
     if getattr(args, "ancestral", None) is not None or getattr(args, "site_rates", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--ancestral and --site-rates exclude --simulate and --distances")
+    if getattr(args, "place", None) is not None or getattr(args, "jplace", None) is not None \
+            or getattr(args, "placed_trees", None) is not None:
+        if getattr(args, "place", None) is None or getattr(args, "jplace", None) is None:
+            raise ValueError("--place and --jplace go together (--placed-trees needs both)")
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--place excludes --simulate and --distances")
+        if getattr(args, "ascertainment", None):
+            raise ValueError("--place with --ascertainment is not implemented")
+        if getattr(args, "keep", 5) < 1:
+            raise ValueError("--keep needs at least one edge")
+        if not os.path.exists(args.place):
+            raise FileNotFoundError("Query file {} does not exist".format(args.place))
     if getattr(args, "fit", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--fit excludes --simulate and --distances")
@@ -303,6 +332,18 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(with_lengths(tm.tree, tm.traversal.brlens).as_newick() + "\n")
+    if getattr(args, "place", None) is not None:
+        from . import place as PL
+        res = tm.place(A.read_fasta(args.place), keep=getattr(args, "keep", 5))
+        placed_on = PL.current_tree(tm)
+        PL.write_jplace(args.jplace, placed_on, res,
+                        invocation="phy --place {} --keep {}".format(
+                            os.path.basename(args.place), getattr(args, "keep", 5)))
+        if getattr(args, "placed_trees", None):
+            with open(args.placed_trees, "w") as fh:
+                for name, rows in zip(res["names"], res["placements"]):
+                    fh.write(PL.attach(placed_on, rows[0]["edge"], name,
+                                       rows[0]["pendant"]).as_newick() + "\n")
     if getattr(args, "support", None) is not None:
         from .support import label_tree, support_label
         from .tree import with_lengths

@@ -76,6 +76,7 @@ class TreeModel(object):
         self.inverse_index = ii
         self.siteweights = sw
         self.names = names
+        self._alphabet = alphabet  # place() encodes query sequences with the same table
         self._tips_owner = None
         self._free()
 
@@ -87,6 +88,7 @@ class TreeModel(object):
         self.siteweights = np.ones(S) if siteweights is None else np.asarray(siteweights)
         self.inverse_index = np.arange(S) if inverse_index is None else np.asarray(inverse_index)
         self.names = dict(names) if isinstance(names, dict) else {n: i for i, n in enumerate(names)}
+        self._alphabet = None  # no character table: place() then needs coded queries
         self._tips_owner = None
         self._free()
 
@@ -101,6 +103,7 @@ class TreeModel(object):
         self.siteweights = np.ones(S) if siteweights is None else np.asarray(siteweights)
         self.inverse_index = np.arange(S)
         self.names = {n: i for i, n in enumerate(names)}
+        self._alphabet = None
         self._tips_owner = None
         self._free()
 
@@ -122,6 +125,7 @@ class TreeModel(object):
         self.siteweights = owner.siteweights
         self.inverse_index = owner.inverse_index
         self.names = owner.names
+        self._alphabet = getattr(owner, "_alphabet", None)
         self.compact_tips = owner.compact_tips
         self._free()
         self._tips_owner = owner
@@ -658,6 +662,14 @@ class TreeModel(object):
         (``modelfit.optimise_model``)."""
         from . import modelfit
         return modelfit.optimise_model(self, params, branch_lengths, max_iter, lnl_tol)
+
+    # ------------------------------------------------------------------ placement
+    def place(self, queries, keep=5, pendant0=None, tol=1e-8, max_iter=50, alphabet=None):
+        """Place query sequences on the model's tree without rebuilding it: every query scored
+        at every edge in one pass, the `keep` best edges of each refined by Newton on the pendant
+        length (``place.place``, pu_place_prescore / pu_place_refine)."""
+        from . import place
+        return place.place(self, queries, keep, pendant0, tol, max_iter, alphabet)
 
     # ------------------------------------------------------------------ simulation
     def simulate(self, n_sites, seed=0, first_site=0, return_categories=False,
