@@ -216,7 +216,8 @@ int pu_optimise_edge(pu_ctx *ctx, int node_a, int node_b, double tol, int max_it
  * utils.py:137-188): rows[n_rows][5]; a row (p, s, g, n, p) re-orients p towards n from s and
  * g, then optimises edge (n, p); (n, c1, c2, -1, -1) restores n; (-1, -1, -1, a, b) optimises
  * edge (a, b).  Ends with a full traversal at the new lengths: lnl_out; evals_out = Newton
- * iterations taken. */
+ * iterations taken.  An error in mid-pass (a row that names no edge, a failed launch) runs that
+ * traversal too, at the lengths reached so far, before the first error is returned. */
 int pu_optimise_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int max_iter,
                       double *lnl_out, int *evals_out);
 /* The reference's own 1-D minimisers on the length of edge (a, b) (r06): method 1 = brent
@@ -258,7 +259,8 @@ int pu_quartet_derivs(pu_ctx *ctx, const int32_t nodes[4], const double lens[5],
  * quartets_out [n_scored][6] = {NOD, PAR, x0, x1, x2, x3}.  *n_scored_out <= n_tips - 3; the
  * buffers hold n_tips - 3 entries.  No length is stored.  The pass ends with a full traversal,
  * so the context's partials, lnL and sitewise lnL are bitwise those of pu_run before the call.
- * PU_E_ARG also for tol <= 0 and max_iter < 0. */
+ * An error in mid-pass (a row that names no edge, a failed launch) runs that traversal too before
+ * the first error is returned.  PU_E_ARG also for tol <= 0 and max_iter < 0. */
 int pu_nni_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, int max_iter,
                  double *scores_out, int32_t *quartets_out, int *n_scored_out);
 /* HIP-event time (ms) of the last k_quartet launch made while pu_ctx_profile was on. */
@@ -293,7 +295,8 @@ int pu_rell_sums_device(int device, void *stream, int n_vec, int64_t n_sites, co
  * support_out[n_scored][4] = {lrt = 2 max(d, 0), alrt_chi2 = erf(sqrt(lrt / 2)),
  * abayes = 1 / sum_k exp(l_k - l_0), sh_alrt = #{r : d > g_r + epsilon} / n_rep}, all NaN where
  * l_0 is not finite; rell_out (nullable) [n_scored][n_rep + 1][3] = B of row w (index 0) and of
- * every replicate.  The context is left as pu_nni_sweep leaves it; no length is stored.
+ * every replicate.  The context is left as pu_nni_sweep leaves it, after an error in mid-pass
+ * too; no length is stored.
  * Refusals as pu_nni_sweep, and PU_E_ARG, before the first launch, for n_rep < 1, a replicate
  * outside [0, 2^32), epsilon negative or non-finite, pattern weights that are negative,
  * non-integer or sum outside [1, 2^31 - 1].  PU_E_NOMEM (the message names the bytes) where the
@@ -327,7 +330,9 @@ int pu_ancestral_edge(pu_ctx *ctx, int node, int other, double length, uint8_t *
  * = n <= n_tips - 2; the buffers hold n_tips - 2 entries, more internal nodes in the rows are
  * PU_E_ARG.  The results stay on the device during the pass and are copied once per array.
  * The pass ends with a full traversal, so the context's partials, lnL and sitewise lnL are
- * bitwise those of pu_run before the call.  Refusals as pu_ancestral_edge. */
+ * bitwise those of pu_run before the call.  An error in mid-pass (a row that names no edge, a
+ * failed launch) runs that traversal too before the first error is returned.  Refusals as
+ * pu_ancestral_edge. */
 int pu_ancestral_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *nodes_out,
                        uint8_t *map_state_out, double *map_prob_out, double *post_out,
                        double *node_lnl_out, int *n_nodes_out);
@@ -367,8 +372,10 @@ int pu_edge_counts(pu_ctx *ctx, int node, int other, double length, double *coun
  * tree's lnL, by the pulley principle), *n_edges_out = n <= 2 n_tips - 3; the buffers hold
  * 2 n_tips - 3 entries, more edges in the rows are PU_E_ARG.  The results stay on the device
  * during the pass and are copied once per array.  The pass ends with a full traversal, so the
- * context's partials, lnL and sitewise lnL are bitwise those of pu_run before the call.
- * Refusals as pu_edge_counts.  (The reference has none) */
+ * context's partials, lnL and sitewise lnL are bitwise those of pu_run before the call.  An
+ * error in mid-pass (a row that names no edge, a failed launch) runs that traversal too before
+ * the first error is returned.  Refusals as pu_edge_counts.  (The reference has none; DESIGN
+ * 4.18.) */
 int pu_counts_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, int32_t *edges_out,
                     double *lengths_out, double *counts_out, double *edge_lnl_out,
                     int *n_edges_out);
@@ -415,7 +422,8 @@ int pu_place_edge(pu_ctx *ctx, int node, int other, double length, int n_query, 
  * *n_edges_out = E <= 2 n_tips - 3; the buffers hold 2 n_tips - 3 edges, more in the rows are
  * PU_E_ARG.  The queries are uploaded once; the scores stay on the device during the pass and
  * are copied once.  The pass ends with a full traversal, so the context's partials, lnL and
- * sitewise lnL are bitwise those of pu_run before the call. */
+ * sitewise lnL are bitwise those of pu_run before the call.  An error in mid-pass (a row that
+ * names no edge, a failed launch) runs that traversal too before the first error is returned. */
 int pu_place_prescore(pu_ctx *ctx, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
                       const uint8_t *query_codes, const int32_t *site_pattern,
                       const double *site_weight, int n_codes, const double *code_table, double l0,

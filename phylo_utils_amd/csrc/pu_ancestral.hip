@@ -29,6 +29,8 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_resident.h"
+#include "pu_service.h"
 
 using namespace pu;
 
@@ -64,8 +66,6 @@ struct AncLds {
         total = vals + (size_t)C * (K + 2) * kLanes;
     }
 };
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
-constexpr int kCtxMaxCat = 64;            // pu_ctx_create takes no more categories
 
 template <int K>
 __global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, AncArgs q) {
@@ -226,45 +226,16 @@ size_t anc_lds_bytes(int K, int C) { return AncLds(K, C).total * sizeof(double);
 // (K = 2: 64, 4: 50, 20: 10)
 int anc_max_cat(int K) {
     int C = 0;
-    while (C < kCtxMaxCat && anc_lds_bytes(K, C + 1) <= kLdsBytes) ++C;
+    while (C < kCtxMaxCat && anc_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
     return C;
 }
 
 bool is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
 
-// a device buffer owned by one call
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { dfree(p); }
-    int alloc(std::string *err, size_t n) { return dalloc(err, &p, n); }
-};
-
-// what every call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
+// what every call needs of the context, and its partial sums
 int ancestral_ready(pu_ctx *c, const char *what) {
-    int rc = edge_prepare(c);
-    if (rc) return rc;
-    if (c->flags & PU_LNL_ONLY)
-        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
-                       "storage)", what);
-    if (c->host_p)
-        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
-                       "(pu_set_model); this context is on host transition matrices", what);
-    if (c->asc_mode)
-        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
-                       "implemented", what);
-    if (c->K != 2 && c->K != 4 && c->K != 20)
-        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
-    if (c->C > anc_max_cat(c->K))
-        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
-                       "one workgroup (at most %d)", what, c->C, c->K, anc_max_cat(c->K));
-    if (c->a_tiles < c->n_tiles) {
-        dfree(c->d_a_part);
-        c->a_tiles = 0;
-        if ((rc = dalloc(&c->err, &c->d_a_part, (size_t)c->n_tiles))) return rc;
-        c->a_tiles = c->n_tiles;
-    }
-    return PU_OK;
+    const int rc = resident_ready(c, what, anc_max_cat(c->K));
+    return rc ? rc : ctx_grow(c, c->d_a_part, c->a_part_cap, (size_t)c->n_tiles);
 }
 
 template <int K>
@@ -279,35 +250,18 @@ int ancestral_enqueue(pu_ctx *c, AncArgs q, double *lnl_dev) {
     EdgeArgs a;
     edge_fill_args(c, a);
     q.part = c->d_a_part;
-    const bool prof = c->profile;
-    if (prof) {
-        for (hipEvent_t &e : c->a_ev)
-            if (!e) HIPCHK(&c->err, hipEventCreate(&e));
-        HIPCHK(&c->err, hipEventRecord(c->a_ev[0], c->stream));
-    }
+    int rc;
+    if ((rc = c->a_timer.begin(c))) return rc;
     switch (c->K) {
         case 2: launch_ancestral_k<2>(c->stream, a, q); break;
         case 4: launch_ancestral_k<4>(c->stream, a, q); break;
         default: launch_ancestral_k<20>(c->stream, a, q); break;
     }
     HIPCHK(&c->err, hipGetLastError());
-    if (prof) HIPCHK(&c->err, hipEventRecord(c->a_ev[1], c->stream));
+    if ((rc = c->a_timer.end(c))) return rc;
     hipLaunchKernelGGL(k_ancestral_sum, dim3(1), dim3(256), 0, c->stream, c->d_a_part,
                        c->n_tiles, lnl_dev);
     HIPCHK(&c->err, hipGetLastError());
-    return PU_OK;
-}
-
-// after the stream has drained: the time of the last launch made while profiling
-int ancestral_stamp(pu_ctx *c) {
-    if (c->profile && c->a_ev[1])
-        HIPCHK(&c->err, hipEventElapsedTime(&c->a_ms, c->a_ev[0], c->a_ev[1]));
-    return PU_OK;
-}
-
-template <class T>
-int to_host(pu_ctx *c, T *dst, const T *src, size_t n) {
-    if (n) HIPCHK(&c->err, hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
     return PU_OK;
 }
 
@@ -341,22 +295,18 @@ int pu_ancestral_edge(pu_ctx *c, int node, int other, double length, uint8_t *ma
         return set_err(&c->err, PU_E_ARG, "pu_ancestral_edge: length %g", length);
     q.t = length < 0.0 ? c->up_len[key] : length;
     const size_t S = (size_t)c->S, K = (size_t)c->K;
-    DevBuf<uint8_t> d_state;
-    DevBuf<double> d_prob, d_post, d_lnl;
-    if ((rc = d_state.alloc(&c->err, S)) || (rc = d_prob.alloc(&c->err, S)) ||
-        (rc = d_post.alloc(&c->err, post ? S * K : 0)) || (rc = d_lnl.alloc(&c->err, 1)))
-        return rc;
-    q.map_state = d_state.p;
-    q.map_prob = d_prob.p;
-    q.post = d_post.p;
-    if ((rc = ancestral_enqueue(c, q, d_lnl.p))) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = ancestral_stamp(c)) || (rc = to_host(c, map_state, d_state.p, S)) ||
-        (rc = to_host(c, map_prob, d_prob.p, S)) ||
-        (rc = to_host(c, post, d_post.p, post ? S * K : 0)) ||
-        (rc = to_host(c, lnl_out, d_lnl.p, 1)))
-        return rc;
-    return PU_OK;
+    HostCall h(c->stream, &c->err);
+    q.map_state = h.alloc<uint8_t>(S);
+    q.map_prob = h.alloc<double>(S);
+    q.post = h.alloc<double>(post ? S * K : 0);
+    double *d_lnl = h.alloc<double>(1);
+    if (!h.rc) h.rc = ancestral_enqueue(c, q, d_lnl);
+    h.to_host(map_state, q.map_state, S);
+    h.to_host(map_prob, q.map_prob, S);
+    h.to_host(post, q.post, post ? S * K : 0);
+    h.to_host(lnl_out, d_lnl, 1);
+    rc = h.finish("pu_ancestral_edge");
+    return rc ? rc : c->a_timer.stamp(c);
 }
 
 int pu_ancestral_sweep(pu_ctx *c, int n_rows, const int32_t *rows, int32_t *nodes_out,
@@ -369,64 +319,49 @@ int pu_ancestral_sweep(pu_ctx *c, int n_rows, const int32_t *rows, int32_t *node
     int rc = ancestral_ready(c, "ancestral reconstruction");
     if (rc) return rc;
     DeviceGuard g(c->device);
-    const int cap = c->n_tips - 2;
-    const size_t S = (size_t)c->S, K = (size_t)c->K;
+    const size_t cap = (size_t)c->n_tips - 2, S = (size_t)c->S, K = (size_t)c->K;
     // the results of all nodes stay on the device until the walk is over
-    DevBuf<uint8_t> d_state;
-    DevBuf<double> d_prob, d_post, d_lnl;
-    if (cap > 0 &&
-        ((rc = d_state.alloc(&c->err, cap * S)) || (rc = d_prob.alloc(&c->err, cap * S)) ||
-         (rc = d_post.alloc(&c->err, post_out ? cap * S * K : 0)) ||
-         (rc = d_lnl.alloc(&c->err, (size_t)cap))))
-        return rc;
-    int count = 0;
+    HostCall h(c->stream, &c->err);
+    uint8_t *d_state = h.alloc<uint8_t>(cap * S);
+    double *d_prob = h.alloc<double>(cap * S);
+    double *d_post = h.alloc<double>(post_out ? cap * S * K : 0);
+    double *d_lnl = h.alloc<double>(cap);
+    if (h.rc) return h.rc;
+    size_t count = 0;
     // reconstruct `node` from `other`, the far end of their edge, on the current partials
     auto visit = [&](int node, int other, int key) -> int {
         if (is_tip(c, node)) return PU_OK;
         if (count >= cap)
             return set_err(&c->err, PU_E_ARG, "pu_ancestral_sweep: more than n_tips - 2 = %d "
-                           "internal nodes in the rows", cap);
+                           "internal nodes in the rows", (int)cap);
         AncArgs q = {};
         int r;
         if ((r = edge_node_src(c, node, &q.n)) || (r = edge_node_src(c, other, &q.o))) return r;
         q.t = c->up_len[key];
-        q.map_state = d_state.p + count * S;
-        q.map_prob = d_prob.p + count * S;
-        q.post = post_out ? d_post.p + count * S * K : nullptr;
-        if ((r = ancestral_enqueue(c, q, d_lnl.p + count))) return r;
+        q.map_state = d_state + count * S;
+        q.map_prob = d_prob + count * S;
+        q.post = post_out ? d_post + count * S * K : nullptr;
+        if ((r = ancestral_enqueue(c, q, d_lnl + count))) return r;
         nodes_out[count++] = node;
         return PU_OK;
     };
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if (row[0] >= 0) {  // re-orient or restore, as pu_optimise_sweep applies them
-            int k1, k2;
-            if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
-                return rc;
-            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
-            if ((rc = edge_update_ops(c, 1, row, bl))) return rc;
-        }
-        if (row[3] < 0) continue;
-        const int nod = row[3], par = row[4];
-        int key;
-        if ((rc = edge_key(c, nod, par, &key))) return rc;
+    return resident_walk(
+        c, n_rows, rows,
         // NOD from PAR, which holds everything but NOD's subtree; on the root edge (row 0) each
         // end is the other's complement
-        if ((rc = visit(nod, par, key))) return rc;
-        if (r == 0 && (rc = visit(par, nod, key))) return rc;
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)count;
-    if ((rc = ancestral_stamp(c)) || (rc = to_host(c, map_state_out, d_state.p, n * S)) ||
-        (rc = to_host(c, map_prob_out, d_prob.p, n * S)) ||
-        (rc = to_host(c, post_out, d_post.p, post_out ? n * S * K : 0)) ||
-        (rc = to_host(c, node_lnl_out, d_lnl.p, n)))
-        return rc;
-    *n_nodes_out = count;
-    // every node is back in its post-order orientation by the restore rows' updates; one
-    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
-    double lnl;
-    return pu_run(c, &lnl, nullptr);
+        [&](int r, const int32_t *row, int key) {
+            const int e = visit(row[3], row[4], key);
+            return e || r != 0 ? e : visit(row[4], row[3], key);
+        },
+        [&] {
+            h.to_host(map_state_out, d_state, count * S);
+            h.to_host(map_prob_out, d_prob, count * S);
+            h.to_host(post_out, d_post, post_out ? count * S * K : 0);
+            h.to_host(node_lnl_out, d_lnl, count);
+            if (const int e = h.finish("pu_ancestral_sweep")) return e;
+            *n_nodes_out = (int)count;
+            return c->a_timer.stamp(c);
+        });
 }
 
 int pu_site_rates(pu_ctx *c, double *cat_post_out, double *mean_rate_out) {
@@ -442,24 +377,20 @@ int pu_site_rates(pu_ctx *c, double *cat_post_out, double *mean_rate_out) {
         return rc;
     q.t = c->up_len[key];
     const size_t S = (size_t)c->S, C = (size_t)c->C;
-    DevBuf<double> d_cat, d_rate, d_lnl;
-    if ((rc = d_cat.alloc(&c->err, cat_post_out ? S * C : 0)) ||
-        (rc = d_rate.alloc(&c->err, S)) || (rc = d_lnl.alloc(&c->err, 1)))
-        return rc;
-    q.cat_post = d_cat.p;
-    q.mean_rate = d_rate.p;
-    if ((rc = ancestral_enqueue(c, q, d_lnl.p))) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = ancestral_stamp(c)) ||
-        (rc = to_host(c, cat_post_out, d_cat.p, cat_post_out ? S * C : 0)) ||
-        (rc = to_host(c, mean_rate_out, d_rate.p, S)))
-        return rc;
-    return PU_OK;
+    HostCall h(c->stream, &c->err);
+    q.cat_post = h.alloc<double>(cat_post_out ? S * C : 0);
+    q.mean_rate = h.alloc<double>(S);
+    double *d_lnl = h.alloc<double>(1);
+    if (!h.rc) h.rc = ancestral_enqueue(c, q, d_lnl);
+    h.to_host(cat_post_out, q.cat_post, cat_post_out ? S * C : 0);
+    h.to_host(mean_rate_out, q.mean_rate, S);
+    rc = h.finish("pu_site_rates");
+    return rc ? rc : c->a_timer.stamp(c);
 }
 
 int pu_ancestral_kernel_ms(pu_ctx *c, double *ms_out) {
     if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
-    *ms_out = (double)c->a_ms;
+    *ms_out = (double)c->a_timer.ms;
     return PU_OK;
 }
 

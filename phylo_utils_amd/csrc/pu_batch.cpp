@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "pu_ctx.h"
+#include "pu_resident.h"
 
 struct pu_batch {
     int device = 0;
@@ -146,7 +147,7 @@ int pu_batch_enqueue(pu_batch *b, double *lnl_dev) {
         lds = std::max(lds, l.lds + (size_t)l.a.lds_pad);
         max_rows = std::max(max_rows, l.pa.n_sides * l.pa.C * l.pa.K);
     }
-    if (lds > 160 * 1024)
+    if (lds > pu::kCuLdsBytes)
         return set_err(&b->err, PU_E_ARG, "LDS request %zu exceeds 160 KiB", lds);
     std::vector<pu::TraverseArgs> ht(n);
     std::vector<pu::PmatArgs> hp(n);

@@ -21,6 +21,7 @@
 
 #include "pu_ctx.h"
 #include "pu_plan.h"
+#include "pu_resident.h"
 
 using pu::OpDesc;
 
@@ -273,7 +274,8 @@ int pu_ctx_create(pu_ctx **out, int device, int n_nodes, int n_tips, int64_t S, 
                   int flags) {
     if (!out) return set_err(nullptr, PU_E_ARG, "null out pointer");
     *out = nullptr;
-    if (n_nodes < 2 || n_tips < 2 || n_tips > n_nodes || S < 1 || C < 1 || C > 64 || K < 2)
+    if (n_nodes < 2 || n_tips < 2 || n_tips > n_nodes || S < 1 || C < 1 || C > pu::kCtxMaxCat ||
+        K < 2)
         return set_err(nullptr, PU_E_ARG, "pu_ctx_create: bad sizes n_nodes=%d n_tips=%d "
                        "S=%lld C=%d K=%d", n_nodes, n_tips, (long long)S, C, K);
     if (!pu::traverse_supported(K))
@@ -871,7 +873,7 @@ int pu::prepare_launch(pu_ctx *c, LaunchPlan &L) {
     }
     const size_t lds = pu::traverse_lds_bytes(c->K, c->C, c->n_codes, c->max_chunk_uses, coded,
                                               c->n_lds);
-    if (lds > 160 * 1024)
+    if (lds > pu::kCuLdsBytes)
         return set_err(&c->err, PU_E_ARG, "LDS request %zu exceeds 160 KiB", lds);
     pu::PmatArgs &pa = L.pa;
     pa = pu::PmatArgs();

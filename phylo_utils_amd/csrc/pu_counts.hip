@@ -42,6 +42,8 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_resident.h"
+#include "pu_service.h"
 
 using namespace pu;
 
@@ -87,8 +89,6 @@ struct CntLds {
         total = stage + (K == 20 ? (size_t)C * 2 * K * kCntPitch : 0);
     }
 };
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
-constexpr int kCtxMaxCat = 64;            // pu_ctx_create takes no more categories
 
 template <int K, bool MFMA>
 __global__ void __launch_bounds__(64 * cnt_max_waves(K)) k_counts(EdgeArgs a, CntArgs q) {
@@ -351,7 +351,7 @@ size_t cnt_lds_bytes(int K, int C) { return CntLds(K, C).total * sizeof(double);
 // 20: 6)
 int cnt_max_cat(int K) {
     int C = 0;
-    while (C < kCtxMaxCat && cnt_lds_bytes(K, C + 1) <= kLdsBytes) ++C;
+    while (C < kCtxMaxCat && cnt_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
     return C;
 }
 
@@ -359,41 +359,10 @@ size_t cnt_part_doubles(const pu_ctx *c) {
     return (size_t)cnt_grid(c->K, c->n_tiles) * ((size_t)c->C * c->K * c->K + 1);
 }
 
-// a device buffer owned by one call
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { dfree(p); }
-    int alloc(std::string *err, size_t n) { return dalloc(err, &p, n); }
-};
-
-// what every call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
-// (pu_ancestral.hip's ancestral_ready)
+// what every call needs of the context, and the workgroups' partials
 int counts_ready(pu_ctx *c, const char *what) {
-    int rc = edge_prepare(c);
-    if (rc) return rc;
-    if (c->flags & PU_LNL_ONLY)
-        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
-                       "storage)", what);
-    if (c->host_p)
-        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
-                       "(pu_set_model); this context is on host transition matrices", what);
-    if (c->asc_mode)
-        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
-                       "implemented", what);
-    if (c->K != 2 && c->K != 4 && c->K != 20)
-        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
-    if (c->C > cnt_max_cat(c->K))
-        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
-                       "one workgroup (at most %d)", what, c->C, c->K, cnt_max_cat(c->K));
-    const size_t need = cnt_part_doubles(c);
-    if (c->c_part_cap < need) {
-        dfree(c->d_c_part);
-        c->c_part_cap = 0;
-        if ((rc = dalloc(&c->err, &c->d_c_part, need))) return rc;
-        c->c_part_cap = need;
-    }
-    return PU_OK;
+    const int rc = resident_ready(c, what, cnt_max_cat(c->K));
+    return rc ? rc : ctx_grow(c, c->d_c_part, c->c_part_cap, cnt_part_doubles(c));
 }
 
 template <int K, bool MFMA>
@@ -418,12 +387,8 @@ int counts_enqueue(pu_ctx *c, CntArgs q, double *counts_dev, double *lnl_dev) {
     EdgeArgs a;
     edge_fill_args(c, a);
     q.part = c->d_c_part;
-    const bool prof = c->profile;
-    if (prof) {
-        for (hipEvent_t &e : c->c_ev)
-            if (!e) HIPCHK(&c->err, hipEventCreate(&e));
-        HIPCHK(&c->err, hipEventRecord(c->c_ev[0], c->stream));
-    }
+    int rc;
+    if ((rc = c->c_timer.begin(c))) return rc;
     switch (c->K) {
         case 2: launch_counts_k<2, false>(c->stream, a, q); break;
         case 4: launch_counts_k<4, false>(c->stream, a, q); break;
@@ -435,22 +400,10 @@ int counts_enqueue(pu_ctx *c, CntArgs q, double *counts_dev, double *lnl_dev) {
             break;
     }
     HIPCHK(&c->err, hipGetLastError());
-    if (prof) HIPCHK(&c->err, hipEventRecord(c->c_ev[1], c->stream));
+    if ((rc = c->c_timer.end(c))) return rc;
     hipLaunchKernelGGL(k_counts_sum, dim3(1), dim3(256), 0, c->stream, c->d_c_part,
                        cnt_grid(c->K, c->n_tiles), c->C * c->K * c->K, counts_dev, lnl_dev);
     HIPCHK(&c->err, hipGetLastError());
-    return PU_OK;
-}
-
-// after the stream has drained: the time of the last launch made while profiling
-int counts_stamp(pu_ctx *c) {
-    if (c->profile && c->c_ev[1])
-        HIPCHK(&c->err, hipEventElapsedTime(&c->c_ms, c->c_ev[0], c->c_ev[1]));
-    return PU_OK;
-}
-
-int to_host(pu_ctx *c, double *dst, const double *src, size_t n) {
-    if (n) HIPCHK(&c->err, hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost));
     return PU_OK;
 }
 
@@ -481,14 +434,13 @@ int pu_edge_counts(pu_ctx *c, int node, int other, double length, double *counts
         return set_err(&c->err, PU_E_ARG, "pu_edge_counts: length %g", length);
     q.t = length < 0.0 ? c->up_len[key] : length;
     const size_t n = (size_t)c->C * c->K * c->K;
-    DevBuf<double> d_out;  // the matrices, then the lnL
-    if ((rc = d_out.alloc(&c->err, n + 1))) return rc;
-    if ((rc = counts_enqueue(c, q, d_out.p, d_out.p + n))) return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = counts_stamp(c)) || (rc = to_host(c, counts_out, d_out.p, n)) ||
-        (rc = to_host(c, lnl_out, d_out.p + n, 1)))
-        return rc;
-    return PU_OK;
+    HostCall h(c->stream, &c->err);
+    double *d_out = h.alloc<double>(n + 1);  // the matrices, then the lnL
+    if (!h.rc) h.rc = counts_enqueue(c, q, d_out, d_out + n);
+    h.to_host(counts_out, d_out, n);
+    h.to_host(lnl_out, d_out + n, 1);
+    rc = h.finish("pu_edge_counts");
+    return rc ? rc : c->c_timer.stamp(c);
 }
 
 int pu_counts_sweep(pu_ctx *c, int n_rows, const int32_t *rows, int32_t *edges_out,
@@ -502,53 +454,44 @@ int pu_counts_sweep(pu_ctx *c, int n_rows, const int32_t *rows, int32_t *edges_o
     if (rc) return rc;
     DeviceGuard g(c->device);
     const int cap = 2 * c->n_tips - 3;
+    size_t n_edges = 0;
+    for (int r = 0; r < n_rows; ++r) n_edges += rows[5 * (size_t)r + 3] >= 0;
+    if (n_edges > (size_t)cap)
+        return set_err(&c->err, PU_E_ARG, "pu_counts_sweep: more than 2 n_tips - 3 = %d edges in "
+                       "the rows", cap);
     const size_t n = (size_t)c->C * c->K * c->K;
     // the results of all edges stay on the device until the walk is over
-    DevBuf<double> d_counts, d_lnl;
-    if ((rc = d_counts.alloc(&c->err, (size_t)cap * n)) ||
-        (rc = d_lnl.alloc(&c->err, (size_t)cap)))
-        return rc;
-    int count = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if (row[0] >= 0) {  // re-orient or restore, as pu_optimise_sweep applies them
-            int k1, k2;
-            if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
-                return rc;
-            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
-            if ((rc = edge_update_ops(c, 1, row, bl))) return rc;
-        }
-        if (row[3] < 0) continue;
-        const int nod = row[3], par = row[4];
-        int key;
-        if ((rc = edge_key(c, nod, par, &key))) return rc;
-        if (count >= cap)
-            return set_err(&c->err, PU_E_ARG, "pu_counts_sweep: more than 2 n_tips - 3 = %d "
-                           "edges in the rows", cap);
-        // i the state at NOD (its subtree), j the state at PAR (everything else)
-        CntArgs q = {};
-        if ((rc = edge_node_src(c, nod, &q.n)) || (rc = edge_node_src(c, par, &q.o))) return rc;
-        q.t = c->up_len[key];
-        if ((rc = counts_enqueue(c, q, d_counts.p + count * n, d_lnl.p + count))) return rc;
-        edges_out[2 * count] = nod;
-        edges_out[2 * count + 1] = par;
-        lengths_out[count] = q.t;
-        ++count;
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = counts_stamp(c)) || (rc = to_host(c, counts_out, d_counts.p, count * n)) ||
-        (rc = to_host(c, edge_lnl_out, d_lnl.p, (size_t)count)))
-        return rc;
-    *n_edges_out = count;
-    // every node is back in its post-order orientation by the restore rows' updates; one
-    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
-    double lnl;
-    return pu_run(c, &lnl, nullptr);
+    HostCall h(c->stream, &c->err);
+    double *d_counts = h.alloc<double>(n_edges * n), *d_lnl = h.alloc<double>(n_edges);
+    if (h.rc) return h.rc;
+    size_t count = 0;
+    return resident_walk(
+        c, n_rows, rows,
+        [&](int, const int32_t *row, int key) {
+            // i the state at NOD (its subtree), j the state at PAR (everything else)
+            CntArgs q = {};
+            int e;
+            if ((e = edge_node_src(c, row[3], &q.n)) || (e = edge_node_src(c, row[4], &q.o)))
+                return e;
+            q.t = c->up_len[key];
+            if ((e = counts_enqueue(c, q, d_counts + count * n, d_lnl + count))) return e;
+            edges_out[2 * count] = row[3];
+            edges_out[2 * count + 1] = row[4];
+            lengths_out[count++] = q.t;
+            return PU_OK;
+        },
+        [&] {
+            h.to_host(counts_out, d_counts, count * n);
+            h.to_host(edge_lnl_out, d_lnl, count);
+            if (const int e = h.finish("pu_counts_sweep")) return e;
+            *n_edges_out = (int)count;
+            return c->c_timer.stamp(c);
+        });
 }
 
 int pu_counts_kernel_ms(pu_ctx *c, double *ms_out) {
     if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
-    *ms_out = (double)c->c_ms;
+    *ms_out = (double)c->c_timer.ms;
     return PU_OK;
 }
 

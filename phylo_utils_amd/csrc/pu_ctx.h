@@ -2,7 +2,9 @@
 // unit shares (pu_capi.cpp: contexts, traversal; pu_edge.cpp: edge likelihoods, derivatives and
 // branch-length optimisation).  The traversal planner is host-only and does not see a context
 // (pu_plan.h).  The host layer of the stateless calls (device buffers, per-device state,
-// host-call scope, pair-call argument rules) is pu_service.h.  Not part of the public ABI.
+// host-call scope, pair-call argument rules) is pu_service.h; that of the calls on the resident
+// partials of a context (limits, refusals, the edge layer's helpers, the walk over the rows of the
+// optimising traversal) is pu_resident.h.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -89,6 +91,21 @@ struct TipStore {
 
 struct SimState;  // pu_simulate.hip: the simulator's device buffers of a context
 struct PlaceState;  // pu_place.hip: the placement tables of a context
+
+// The HIP-event time of the last launch of one kernel while the context is profiling
+// (pu_ctx_profile): begin and end are recorded round the launch, on the context's stream, and
+// stamp reads the time once the launch has ended -- it waits for the closing event, which costs
+// nothing after the stream has drained.  All three do nothing when the context is not profiling
+// or nothing is pending.  Bodies in pu_edge.cpp.
+struct LaunchTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool pending = false;  // a pair was recorded since the last stamp
+    float ms = 0.f;
+    int begin(pu_ctx *c);
+    int end(pu_ctx *c);
+    int stamp(pu_ctx *c);
+    void destroy();
+};
 
 }  // namespace pu
 
@@ -217,25 +234,22 @@ struct pu_ctx {
     bool nt_fresh = false;
     std::vector<hipEvent_t> edge_ev;  // profiling: event pairs around edge reductions
     int n_edge_prof = 0;
-    // quartet scoring (pu_nni.hip): per-workgroup sums [q_tiles][9], the 9 results in mapped
-    // host memory, and the HIP-event time of the last k_quartet launch when profiling
+    // quartet scoring (pu_nni.hip): per-workgroup sums [n_tiles][9] (q_part_cap doubles), the 9
+    // results in mapped host memory, and the time of the last k_quartet launch
     double *d_q_part = nullptr;
-    int q_tiles = 0;
+    size_t q_part_cap = 0;
     double *h_q_res = nullptr, *d_q_res_host = nullptr;
-    hipEvent_t q_ev[2] = {nullptr, nullptr};
-    float q_ms = 0.f;
-    // ancestral reconstruction (pu_ancestral.hip): per-workgroup lnL sums [a_tiles], and the
-    // HIP-event time of the last k_ancestral launch when profiling
+    pu::LaunchTimer q_timer;
+    // ancestral reconstruction (pu_ancestral.hip): per-workgroup lnL sums [n_tiles]
+    // (a_part_cap doubles), and the time of the last k_ancestral launch
     double *d_a_part = nullptr;
-    int a_tiles = 0;
-    hipEvent_t a_ev[2] = {nullptr, nullptr};
-    float a_ms = 0.f;
+    size_t a_part_cap = 0;
+    pu::LaunchTimer a_timer;
     // per-edge joint counts (pu_counts.hip): the workgroups' partial matrices and lnL sums
-    // [c_part_cap] doubles, and the HIP-event time of the last k_counts launch when profiling
+    // (c_part_cap doubles), and the time of the last k_counts launch
     double *d_c_part = nullptr;
     size_t c_part_cap = 0;
-    hipEvent_t c_ev[2] = {nullptr, nullptr};
-    float c_ms = 0.f;
+    pu::LaunchTimer c_timer;
 
     // Lewis ascertainment-bias correction (tree_model.py:92-98, 151-156, 209-214): mode 0 off,
     // 1 the reference's form, 2 weighted; the dummy invariant sites are [asc_first, S)
@@ -285,14 +299,6 @@ int refresh_host_p(pu_ctx *c);
 int ensure_host_p(pu_ctx *c);
 // pu_edge.cpp: release the edge-operation buffers of a context
 void edge_free(pu_ctx *c);
-// pu_edge.cpp, for pu_nni.hip: the edge calls' readiness checks and buffers (prepare), a
-// node's source, the key of edge (u, v) into up_len, the kernels' common arguments, and n
-// in-place updates (par, c1, c2) at lengths brlens[n][2], queued on the context's stream
-int edge_prepare(pu_ctx *c);
-int edge_node_src(pu_ctx *c, int node, NodeSrc *out);
-int edge_key(pu_ctx *c, int u, int v, int *key);
-void edge_fill_args(const pu_ctx *c, EdgeArgs &a);
-int edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens);
 // pu_simulate.hip: release the simulator's buffers of a context
 void sim_free(pu_ctx *c);
 // pu_place.hip: release the placement buffers of a context

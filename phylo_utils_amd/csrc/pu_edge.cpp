@@ -18,6 +18,7 @@
 
 #include "pu_ctx.h"
 #include "pu_minimise.h"
+#include "pu_resident.h"
 
 using namespace pu;
 
@@ -231,7 +232,7 @@ int run_reduce(pu_ctx *c, int mode, const NodeSrc &sa, const NodeSrc &sb, double
         if (!rc) rc = upload_pm(c, m, a);
         if (rc) return rc;
     }
-    if (edge_lds_bytes(mode, c->K, c->C) > 160 * 1024)
+    if (edge_lds_bytes(mode, c->K, c->C) > kCuLdsBytes)
         return set_err(&c->err, PU_E_ARG, "edge operation: C=%d categories of K=%d states "
                        "exceed the LDS of one workgroup", c->C, c->K);
     hipEvent_t *ev = nullptr;
@@ -575,7 +576,7 @@ int push_lengths(pu_ctx *c) {
 int update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens) {
     EdgeArgs a;
     fill_args(c, a);
-    if (edge_lds_bytes(EDGE_UPDATE, c->K, c->C) > 160 * 1024)
+    if (edge_lds_bytes(EDGE_UPDATE, c->K, c->C) > kCuLdsBytes)
         return set_err(&c->err, PU_E_ARG, "edge operation: too many categories for LDS");
     int k = 0;
     for (int o = 0; o < n; ++o) {
@@ -623,13 +624,86 @@ int update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens) {
 
 int pu::flush_lengths(pu_ctx *c) { return c->lengths_dirty ? push_lengths(c) : PU_OK; }
 
-// the edge layer's helpers for pu_nni.hip (quartet scoring on the same resident partials)
+// ---- pu_resident.h: the host layer of the calls on the same resident partials ----------------
+
 int pu::edge_prepare(pu_ctx *c) { return prepare(c); }
 int pu::edge_node_src(pu_ctx *c, int node, NodeSrc *out) { return node_src(c, node, out); }
 int pu::edge_key(pu_ctx *c, int u, int v, int *key) { return edge_of(c, u, v, key); }
 void pu::edge_fill_args(const pu_ctx *c, EdgeArgs &a) { fill_args(c, a); }
 int pu::edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens) {
     return update_ops(c, n, ops, brlens);
+}
+
+int pu::resident_ready(pu_ctx *c, const char *what, int max_cat) {
+    int rc = prepare(c);
+    if (rc) return rc;
+    if (c->flags & PU_LNL_ONLY)
+        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
+                       "storage)", what);
+    if (c->host_p)
+        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
+                       "(pu_set_model); this context is on host transition matrices", what);
+    if (c->asc_mode)
+        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
+                       "implemented", what);
+    if (c->K != 2 && c->K != 4 && c->K != 20)
+        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
+    if (c->C > max_cat)
+        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
+                       "one workgroup (at most %d)", what, c->C, c->K, max_cat);
+    return PU_OK;
+}
+
+int pu::walk_row(pu_ctx *c, const int32_t *row, int *key) {
+    int rc;
+    if (row[0] >= 0) {
+        int k1, k2;
+        if ((rc = edge_of(c, row[0], row[1], &k1)) || (rc = edge_of(c, row[0], row[2], &k2)))
+            return rc;
+        const double bl[2] = {c->up_len[k1], c->up_len[k2]};
+        if ((rc = update_ops(c, 1, row, bl))) return rc;
+    }
+    *key = -1;
+    return row[3] < 0 ? PU_OK : edge_of(c, row[3], row[4], key);
+}
+
+int pu::walk_close(pu_ctx *c, int rc, bool moved_lengths, double *lnl_out) {
+    const std::string first = c->err;
+    double lnl;
+    int rc_run = moved_lengths ? push_lengths(c) : PU_OK;
+    if (!rc_run) rc_run = pu_run(c, rc || !lnl_out ? &lnl : lnl_out, nullptr);
+    return rc ? set_err(&c->err, rc, "%s", first.c_str()) : rc_run;
+}
+
+int LaunchTimer::begin(pu_ctx *c) {
+    if (!c->profile) return PU_OK;
+    for (hipEvent_t &e : ev)
+        if (!e) HIPCHK(&c->err, hipEventCreate(&e));
+    HIPCHK(&c->err, hipEventRecord(ev[0], c->stream));
+    return PU_OK;
+}
+
+int LaunchTimer::end(pu_ctx *c) {
+    if (!c->profile) return PU_OK;
+    HIPCHK(&c->err, hipEventRecord(ev[1], c->stream));
+    pending = true;
+    return PU_OK;
+}
+
+int LaunchTimer::stamp(pu_ctx *c) {
+    if (!c->profile || !pending) return PU_OK;
+    HIPCHK(&c->err, hipEventSynchronize(ev[1]));
+    HIPCHK(&c->err, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    pending = false;
+    return PU_OK;
+}
+
+void LaunchTimer::destroy() {
+    for (hipEvent_t &e : ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    pending = false;
 }
 
 int pu::enqueue_ascbias(pu_ctx *c, double *lnl) {
@@ -677,25 +751,16 @@ void pu::edge_free(pu_ctx *c) {
     }
     c->edge_tiles = 0;
     dfree(c->d_q_part);
-    c->q_tiles = 0;
+    c->q_part_cap = 0;
     if (c->h_q_res) (void)hipHostFree(c->h_q_res);
     c->h_q_res = nullptr;
-    for (hipEvent_t &e : c->q_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    c->q_timer.destroy();
     dfree(c->d_a_part);
-    c->a_tiles = 0;
-    for (hipEvent_t &e : c->a_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    c->a_part_cap = 0;
+    c->a_timer.destroy();
     dfree(c->d_c_part);
     c->c_part_cap = 0;
-    for (hipEvent_t &e : c->c_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    c->c_timer.destroy();
 }
 
 extern "C" {
@@ -767,28 +832,22 @@ int pu_optimise_sweep(pu_ctx *c, int n_rows, const int32_t *rows, double tol, in
     if (rc) return rc;
     DeviceGuard g(c->device);
     int total_iters = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if (row[0] >= 0) {
-            // re-orient (rows (PAR, SIB, GPA, NOD, PAR)) or restore (NOD, CH1, CH2, -1, -1)
-            int k1, k2;
-            if ((rc = edge_of(c, row[0], row[1], &k1)) || (rc = edge_of(c, row[0], row[2], &k2)))
-                return rc;
-            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
-            if ((rc = update_ops(c, 1, row, bl))) return rc;
-        }
-        if (row[3] >= 0) {
-            int key, it = 0;
-            if ((rc = edge_of(c, row[3], row[4], &key))) return rc;
+    // rows (PAR, SIB, GPA, NOD, PAR) re-orient and optimise, rows (NOD, CH1, CH2, -1, -1)
+    // restore; the closing traversal runs at the new lengths, after an error at those reached
+    return resident_walk(
+        c, n_rows, rows,
+        [&](int, const int32_t *row, int key) {
+            int it = 0;
             double t = c->up_len[key];
-            if ((rc = newton(c, row[3], row[4], key, tol, max_iter, &t, nullptr, &it))) return rc;
+            const int r = newton(c, row[3], row[4], key, tol, max_iter, &t, nullptr, &it);
             total_iters += it;
-        }
-    }
-    if (evals_out) *evals_out = total_iters;
-    // every node is back in its post-order orientation; one traversal with the new lengths
-    if ((rc = push_lengths(c))) return rc;
-    return pu_run(c, lnl_out, nullptr);
+            return r;
+        },
+        [&] {
+            if (evals_out) *evals_out = total_iters;
+            return PU_OK;
+        },
+        true, lnl_out);
 }
 
 int pu_minimise_edge(pu_ctx *c, int node_a, int node_b, int method, double lo, double t0,

@@ -27,6 +27,7 @@
 #include "pu_internal.h"
 #include "pu_edge_dev.h"
 #include "pu_minimise.h"
+#include "pu_resident.h"
 
 #include <math.h>
 
@@ -1000,7 +1001,7 @@ size_t edge_lds_bytes(int mode, int K, int C) { return EdgeLds(mode, K, C).total
 
 int launch_edge(hipStream_t st, int mode, const EdgeArgs &a, hipEvent_t after_edge) {
     const size_t lds = edge_lds_bytes(mode, a.K, a.C);
-    if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+    if (lds > kCuLdsBytes) return (int)hipErrorInvalidValue;
     switch (a.K) {
         case 2: return launch_edge_k<2>(st, mode, a, lds, after_edge);
         case 4: return launch_edge_k<4>(st, mode, a, lds, after_edge);

@@ -33,6 +33,7 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_resident.h"
 #include "pu_service.h"
 
 using namespace pu;
@@ -76,7 +77,6 @@ struct QuartetLds {
         total = vals + (size_t)12 * C * kLanes;
     }
 };
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
 
 // the other two nodes of arrangement k = (x0, x_{k+1} | x_c, x_d)
 __host__ __device__ constexpr int arr_c(int k) { return k == 0 ? 2 : 1; }
@@ -257,37 +257,16 @@ size_t quartet_lds_bytes(int K, int C) { return QuartetLds(K, C).total * sizeof(
 // the largest C whose tables and mix area fit the LDS of a CU (K = 2: 25, 4: 24, 20: 19)
 int quartet_max_cat(int K) {
     int C = 0;
-    while (quartet_lds_bytes(K, C + 1) <= kLdsBytes) ++C;
+    while (quartet_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
     return C;
 }
 
 int node_is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
 
-// what every quartet call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
+// what every quartet call needs of the context, its partial sums and its mapped result buffer
 int quartet_ready(pu_ctx *c) {
-    int rc = edge_prepare(c);
-    if (rc) return rc;
-    if (c->flags & PU_LNL_ONLY)
-        return set_err(&c->err, PU_E_STATE, "quartet scoring needs PU_KEEP_PARTIALS "
-                       "(PU_LNL_ONLY reuses CLV storage)");
-    if (c->host_p)
-        return set_err(&c->err, PU_E_STATE, "quartet scoring needs an eigen-decomposed model "
-                       "(pu_set_model); this context is on host transition matrices");
-    if (c->asc_mode)
-        return set_err(&c->err, PU_E_STATE, "quartet scoring with the ascertainment-bias "
-                       "correction is not implemented");
-    if (c->K != 2 && c->K != 4 && c->K != 20)
-        return set_err(&c->err, PU_E_ARG, "quartet scoring: K=%d is not supported", c->K);
-    if (c->C > quartet_max_cat(c->K))
-        return set_err(&c->err, PU_E_ARG, "quartet scoring: C=%d categories of K=%d states "
-                       "exceed the LDS of one workgroup (at most %d)", c->C, c->K,
-                       quartet_max_cat(c->K));
-    if (c->q_tiles < c->n_tiles) {
-        dfree(c->d_q_part);
-        c->q_tiles = 0;
-        if ((rc = dalloc(&c->err, &c->d_q_part, 9 * (size_t)c->n_tiles))) return rc;
-        c->q_tiles = c->n_tiles;
-    }
+    int rc = resident_ready(c, "quartet scoring", quartet_max_cat(c->K));
+    if (rc || (rc = ctx_grow(c, c->d_q_part, c->q_part_cap, 9 * (size_t)c->n_tiles))) return rc;
     if (!c->h_q_res) {
         HIPCHK(&c->err, hipHostMalloc((void **)&c->h_q_res, 9 * sizeof(double),
                                       hipHostMallocMapped));
@@ -321,31 +300,21 @@ int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, 
     q.part = c->d_q_part;
     q.site = d_site;
     q.site_ld = site_ld;
-    const bool prof = c->profile;
-    if (prof) {
-        for (hipEvent_t &e : c->q_ev)
-            if (!e) HIPCHK(&c->err, hipEventCreate(&e));
-        HIPCHK(&c->err, hipEventRecord(c->q_ev[0], c->stream));
-    }
+    int rc;
+    if ((rc = c->q_timer.begin(c))) return rc;
     switch (c->K) {
         case 2: launch_quartet_k<2>(c->stream, a, q); break;
         case 4: launch_quartet_k<4>(c->stream, a, q); break;
         default: launch_quartet_k<20>(c->stream, a, q); break;
     }
     HIPCHK(&c->err, hipGetLastError());
-    if (prof) HIPCHK(&c->err, hipEventRecord(c->q_ev[1], c->stream));
-    if (!out9) {
-        if (prof) {
-            HIPCHK(&c->err, hipEventSynchronize(c->q_ev[1]));
-            HIPCHK(&c->err, hipEventElapsedTime(&c->q_ms, c->q_ev[0], c->q_ev[1]));
-        }
-        return PU_OK;
-    }
+    if ((rc = c->q_timer.end(c))) return rc;
+    if (!out9) return c->q_timer.stamp(c);
     hipLaunchKernelGGL(k_quartet_sum, dim3(1), dim3(256), 0, c->stream, c->d_q_part, c->n_tiles,
                        c->d_q_res_host);
     HIPCHK(&c->err, hipGetLastError());
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if (prof) HIPCHK(&c->err, hipEventElapsedTime(&c->q_ms, c->q_ev[0], c->q_ev[1]));
+    if ((rc = c->q_timer.stamp(c))) return rc;
     for (int k = 0; k < 9; ++k) out9[k] = c->h_q_res[k];
     return PU_OK;
 }
@@ -628,7 +597,6 @@ int sweep_check(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, doub
 int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, double tol,
                int max_iter, double *scores_out, int32_t *quartets_out, int *n_scored_out,
                double *d_site, int64_t site_ld) {
-    int rc;
     // the children of every internal node, in the caller's order (pu_set_schedule's ops)
     std::vector<int> child(2 * (size_t)c->n_nodes, -1);
     for (int o = 0; o < c->n_ops; ++o) {
@@ -637,20 +605,10 @@ int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, doubl
     }
     const int cap = c->n_tips - 3;
     int n_scored = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if (row[0] >= 0) {  // re-orient or restore, as pu_optimise_sweep applies them
-            int k1, k2;
-            if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
-                return rc;
-            const double bl[2] = {c->up_len[k1], c->up_len[k2]};
-            if ((rc = edge_update_ops(c, 1, row, bl))) return rc;
-        }
-        if (row[3] < 0) continue;
+    auto score = [&](int, const int32_t *row, int kc) -> int {
+        int rc;
         const int nod = row[3], par = row[4];
-        int kc;
-        if ((rc = edge_key(c, nod, par, &kc))) return rc;
-        if (node_is_tip(c, nod) || node_is_tip(c, par)) continue;
+        if (node_is_tip(c, nod) || node_is_tip(c, par)) return PU_OK;
         // the quartet (children of NOD | SIB, GPA); on the root edge both are PAR's children
         const int nodes[4] = {child[2 * (size_t)nod], child[2 * (size_t)nod + 1],
                               row[0] >= 0 ? row[1] : child[2 * (size_t)par],
@@ -698,12 +656,13 @@ int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, doubl
                 return rc;
         }
         ++n_scored;
-    }
-    *n_scored_out = n_scored;
-    // every node is back in its post-order orientation by the restore rows' updates; one
-    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
-    double lnl;
-    return pu_run(c, &lnl, nullptr);
+        return PU_OK;
+    };
+    // every score came back to the host with its evaluation: nothing is left to collect
+    return resident_walk(c, n_rows, rows, score, [&] {
+        *n_scored_out = n_scored;
+        return PU_OK;
+    });
 }
 
 }  // namespace
@@ -712,7 +671,7 @@ extern "C" {
 
 int pu_quartet_kernel_ms(pu_ctx *c, double *ms_out) {
     if (!c || !ms_out) return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
-    *ms_out = (double)c->q_ms;
+    *ms_out = (double)c->q_timer.ms;
     return PU_OK;
 }
 

@@ -38,12 +38,14 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_resident.h"
+#include "pu_service.h"
 
 using namespace pu;
 
 namespace {
 
-constexpr int kMaxCodes = 32;      // rows of a query code table
+// (rows of a query code table at most: pu_service.h's kMaxCodes)
 constexpr int kPlaceMaxWaves = 8;  // k_place_table
 constexpr int kPlaceChunk = 2048;  // sites per k_place_prescore workgroup: a constant, so that a
                                    // query's sum order depends on nothing else
@@ -55,8 +57,6 @@ constexpr int kNewtonThreads = 1024;
 constexpr int kPlaceMaxCK = 256;    // C * K of any context the table kernel takes (64 x 4)
 constexpr double kMinLen = 1e-8;    // pu_edge.cpp kMinLen / kMaxLen
 constexpr double kMaxLen = 100.0;
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of one CU, all of which one workgroup may use
-constexpr int kCtxMaxCat = 64;            // pu_ctx_create takes no more categories
 
 __host__ __device__ inline int place_waves(int C) {
     return C < kPlaceMaxWaves ? C : kPlaceMaxWaves;
@@ -424,41 +424,19 @@ size_t place_lds_bytes(int K, int C) { return PlaceLds(K, C).total * sizeof(doub
 // the largest C whose tables fit the LDS of a CU and a context can hold
 int place_max_cat(int K) {
     int C = 0;
-    while (C < kCtxMaxCat && (C + 1) * K <= kPlaceMaxCK && place_lds_bytes(K, C + 1) <= kLdsBytes)
+    while (C < kCtxMaxCat && (C + 1) * K <= kPlaceMaxCK && place_lds_bytes(K, C + 1) <= kCuLdsBytes)
         ++C;
     return C;
-}
-
-// a device buffer owned by one call
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { dfree(p); }
-    int alloc(std::string *err, size_t n) { return dalloc(err, &p, n); }
-};
-
-// a device buffer of the context that only grows
-template <class T>
-int grow(pu_ctx *c, T *&p, size_t &cap, size_t need) {
-    if (cap >= need) return PU_OK;
-    dfree(p);
-    cap = 0;
-    int rc = dalloc(&c->err, &p, need);
-    if (rc) return rc;
-    cap = need;
-    return PU_OK;
 }
 
 }  // namespace
 
 // the placement buffers of a context: the tables of the edge the walk stands on, the chunk
-// sums, and the HIP events of the last launches when profiling
+// sums, and the times of the last launches when profiling
 struct pu::PlaceState {
     double *d_W = nullptr, *d_m = nullptr, *d_G = nullptr, *d_u = nullptr, *d_part = nullptr;
     size_t W_cap = 0, m_cap = 0, G_cap = 0, u_cap = 0, part_cap = 0;
-    hipEvent_t ev[3][2] = {};
-    bool stamped[3] = {};  // a pair was recorded since the last stamp
-    float ms[3] = {};      // table, prescore, newton
+    LaunchTimer timer[3];  // table, prescore, newton
 };
 
 void pu::place_free(pu_ctx *c) {
@@ -469,40 +447,22 @@ void pu::place_free(pu_ctx *c) {
     dfree(s->d_G);
     dfree(s->d_u);
     dfree(s->d_part);
-    for (auto &pair : s->ev)
-        for (hipEvent_t &e : pair)
-            if (e) (void)hipEventDestroy(e);
+    for (LaunchTimer &t : s->timer) t.destroy();
     delete s;
     c->place = nullptr;
 }
 
 namespace {
 
-// what every call needs of the context; PU_E_STATE / PU_E_ARG as the header lists them
-// (pu_ancestral.hip's ancestral_ready)
+// what every call needs of the context, and the host's copy of the eigen-system
 int place_ready(pu_ctx *c, const char *what) {
-    int rc = edge_prepare(c);
-    if (rc) return rc;
-    if (c->flags & PU_LNL_ONLY)
-        return set_err(&c->err, PU_E_STATE, "%s needs PU_KEEP_PARTIALS (PU_LNL_ONLY reuses CLV "
-                       "storage)", what);
-    if (c->host_p)
-        return set_err(&c->err, PU_E_STATE, "%s needs an eigen-decomposed reversible model "
-                       "(pu_set_model); this context is on host transition matrices", what);
-    if (c->asc_mode)
-        return set_err(&c->err, PU_E_STATE, "%s with the ascertainment-bias correction is not "
-                       "implemented", what);
-    if (c->K != 2 && c->K != 4 && c->K != 20)
-        return set_err(&c->err, PU_E_ARG, "%s: K=%d is not supported", what, c->K);
-    if (c->C > place_max_cat(c->K))
-        return set_err(&c->err, PU_E_ARG, "%s: C=%d categories of K=%d states exceed the LDS of "
-                       "one workgroup (at most %d)", what, c->C, c->K, place_max_cat(c->K));
+    if (int rc = resident_ready(c, what, place_max_cat(c->K))) return rc;
     if (c->h_eig.size() != (size_t)(2 * c->K * c->K + c->K))
         return set_err(&c->err, PU_E_STATE, "%s: no eigen-system in the context", what);
     return PU_OK;
 }
 
-// the caller's queries: checked on the host, then uploaded once
+// the caller's queries: checked on the host, then uploaded once as temporaries of the call
 struct QueryHost {
     int n_query;
     int64_t n_sites;
@@ -512,13 +472,6 @@ struct QueryHost {
     int n_codes;
     const double *table;
     double l0;
-};
-
-struct QuerySet {
-    DevBuf<uint8_t> codes;
-    DevBuf<int32_t> map;
-    DevBuf<double> sw;
-    QueryDev d = {};
 };
 
 int check_queries(pu_ctx *c, const char *fn, const QueryHost &h) {
@@ -550,21 +503,19 @@ int check_queries(pu_ctx *c, const char *fn, const QueryHost &h) {
 
 // the queries and u(code) = V^-1 table[code] to the device; the context's buffers sized for
 // them (with_G: the log table and the chunk sums of the pre-score)
-int upload_queries(pu_ctx *c, const QueryHost &h, bool with_G, QuerySet &qs) {
+int upload_queries(pu_ctx *c, const QueryHost &h, bool with_G, HostCall &hc, QueryDev &d) {
     if (!c->place) c->place = new PlaceState();
     PlaceState *s = c->place;
     const int K = c->K;
     const size_t S = (size_t)c->S, n = (size_t)h.n_query * h.n_sites;
     const int n_chunks = (int)((h.n_sites + kPlaceChunk - 1) / kPlaceChunk);
     int rc;
-    if ((rc = qs.codes.alloc(&c->err, n)) ||
-        (rc = qs.map.alloc(&c->err, h.map ? (size_t)h.n_sites : 0)) ||
-        (rc = qs.sw.alloc(&c->err, h.sw ? (size_t)h.n_sites : 0)) ||
-        (rc = grow(c, s->d_W, s->W_cap, S * c->C * K)) || (rc = grow(c, s->d_m, s->m_cap, S)) ||
-        (rc = grow(c, s->d_u, s->u_cap, (size_t)kMaxCodes * K)))
+    if ((rc = ctx_grow(c, s->d_W, s->W_cap, S * c->C * K)) ||
+        (rc = ctx_grow(c, s->d_m, s->m_cap, S)) ||
+        (rc = ctx_grow(c, s->d_u, s->u_cap, (size_t)kMaxCodes * K)))
         return rc;
-    if (with_G && ((rc = grow(c, s->d_G, s->G_cap, S * kMaxCodes)) ||
-                   (rc = grow(c, s->d_part, s->part_cap, (size_t)h.n_query * n_chunks))))
+    if (with_G && ((rc = ctx_grow(c, s->d_G, s->G_cap, S * kMaxCodes)) ||
+                   (rc = ctx_grow(c, s->d_part, s->part_cap, (size_t)h.n_query * n_chunks))))
         return rc;
     std::vector<double> u((size_t)h.n_codes * K);
     const double *iv = c->h_eig.data() + (size_t)K * K + K;
@@ -574,45 +525,21 @@ int upload_queries(pu_ctx *c, const QueryHost &h, bool with_G, QuerySet &qs) {
             for (int j = 0; j < K; ++j) acc += iv[k * K + j] * h.table[(size_t)code * K + j];
             u[(size_t)code * K + k] = acc;
         }
-    HIPCHK(&c->err, hipMemcpyAsync(qs.codes.p, h.codes, n, hipMemcpyHostToDevice, c->stream));
-    if (h.map)
-        HIPCHK(&c->err, hipMemcpyAsync(qs.map.p, h.map, (size_t)h.n_sites * sizeof(int32_t),
-                                       hipMemcpyHostToDevice, c->stream));
-    if (h.sw)
-        HIPCHK(&c->err, hipMemcpyAsync(qs.sw.p, h.sw, (size_t)h.n_sites * sizeof(double),
-                                       hipMemcpyHostToDevice, c->stream));
-    HIPCHK(&c->err, hipMemcpyAsync(s->d_u, u.data(), u.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, c->stream));
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));  // u leaves scope
-    qs.d.codes = qs.codes.p;
-    qs.d.map = qs.map.p;
-    qs.d.sw = qs.sw.p;
-    qs.d.n_sites = h.n_sites;
-    qs.d.n_codes = h.n_codes;
-    qs.d.n_chunks = n_chunks;
-    return PU_OK;
-}
-
-// HIP events around launch `which` (0 table, 1 prescore, 2 newton) while profiling
-int mark(pu_ctx *c, int which, int end) {
-    if (!c->profile) return PU_OK;
-    PlaceState *s = c->place;
-    hipEvent_t &e = s->ev[which][end];
-    if (!e) HIPCHK(&c->err, hipEventCreate(&e));
-    HIPCHK(&c->err, hipEventRecord(e, c->stream));
-    if (end) s->stamped[which] = true;
-    return PU_OK;
+    d.codes = hc.to_device(h.codes, n);
+    d.map = hc.to_device(h.map, (size_t)h.n_sites);
+    d.sw = hc.to_device(h.sw, (size_t)h.n_sites);
+    d.n_sites = h.n_sites;
+    d.n_codes = h.n_codes;
+    d.n_chunks = n_chunks;
+    hc.hip("hipMemcpyAsync", hipMemcpyAsync(s->d_u, u.data(), u.size() * sizeof(double),
+                                            hipMemcpyHostToDevice, hc.st));
+    return hc.finish("placement");  // u leaves scope
 }
 
 // after the stream has drained: the times of the last launches made while profiling
 int place_stamp(pu_ctx *c) {
-    PlaceState *s = c->place;
-    if (!c->profile || !s) return PU_OK;
-    for (int k = 0; k < 3; ++k)
-        if (s->stamped[k]) {
-            HIPCHK(&c->err, hipEventElapsedTime(&s->ms[k], s->ev[k][0], s->ev[k][1]));
-            s->stamped[k] = false;
-        }
+    for (LaunchTimer &t : c->place->timer)
+        if (int rc = t.stamp(c)) return rc;
     return PU_OK;
 }
 
@@ -638,39 +565,39 @@ int table_enqueue(pu_ctx *c, NodeSrc n, NodeSrc o, double t, const QueryHost &h,
     q.m = s->d_m;
     q.G = with_G ? s->d_G : nullptr;
     int rc;
-    if ((rc = mark(c, 0, 0))) return rc;
+    if ((rc = s->timer[0].begin(c))) return rc;
     switch (c->K) {
         case 2: launch_table_k<2>(c->stream, a, q); break;
         case 4: launch_table_k<4>(c->stream, a, q); break;
         default: launch_table_k<20>(c->stream, a, q); break;
     }
     HIPCHK(&c->err, hipGetLastError());
-    return mark(c, 0, 1);
+    return s->timer[0].end(c);
 }
 
 // the pre-score of all queries on the tables in place: score_dev[Q]
-int prescore_enqueue(pu_ctx *c, const QuerySet &qs, int n_query, double *score_dev) {
+int prescore_enqueue(pu_ctx *c, const QueryDev &d, int n_query, double *score_dev) {
     PlaceState *s = c->place;
-    const int64_t blocks = (int64_t)n_query * qs.d.n_chunks;
+    const int64_t blocks = (int64_t)n_query * d.n_chunks;
     if (blocks > 0x7fffffffLL)
         return set_err(&c->err, PU_E_ARG, "placement: %d queries x %d chunks exceed one launch",
-                       n_query, qs.d.n_chunks);
+                       n_query, d.n_chunks);
     int rc;
-    if ((rc = mark(c, 1, 0))) return rc;
+    if ((rc = s->timer[1].begin(c))) return rc;
     hipLaunchKernelGGL(k_place_prescore, dim3((unsigned)blocks), dim3(kPlaceThreads), 0, c->stream,
-                       qs.d, n_query, s->d_G, s->d_part);
+                       d, n_query, s->d_G, s->d_part);
     HIPCHK(&c->err, hipGetLastError());
-    if ((rc = mark(c, 1, 1))) return rc;
+    if ((rc = s->timer[1].end(c))) return rc;
     hipLaunchKernelGGL(k_place_chunk_sum, dim3((unsigned)((n_query + kPlaceThreads - 1) /
                                                           kPlaceThreads)),
-                       dim3(kPlaceThreads), 0, c->stream, s->d_part, n_query, qs.d.n_chunks,
+                       dim3(kPlaceThreads), 0, c->stream, s->d_part, n_query, d.n_chunks,
                        score_dev);
     HIPCHK(&c->err, hipGetLastError());
     return PU_OK;
 }
 
 // k_place_newton for n queries (list_dev, nullptr: 0..n-1) on the tables in place: out_dev[n][5]
-int newton_enqueue(pu_ctx *c, const QuerySet &qs, const int32_t *list_dev, int n, double l0,
+int newton_enqueue(pu_ctx *c, const QueryDev &d, const int32_t *list_dev, int n, double l0,
                    double tol, int max_iter, double *out_dev) {
     PlaceState *s = c->place;
     NewtonArgsP a = {};
@@ -686,42 +613,15 @@ int newton_enqueue(pu_ctx *c, const QuerySet &qs, const int32_t *list_dev, int n
     a.max_iter = max_iter;
     a.out = out_dev;
     int rc;
-    if ((rc = mark(c, 2, 0))) return rc;
+    if ((rc = s->timer[2].begin(c))) return rc;
     const dim3 grid((unsigned)n), block(kNewtonThreads);
     switch (c->K) {
-        case 2: hipLaunchKernelGGL(k_place_newton<2>, grid, block, 0, c->stream, qs.d, a); break;
-        case 4: hipLaunchKernelGGL(k_place_newton<4>, grid, block, 0, c->stream, qs.d, a); break;
-        default: hipLaunchKernelGGL(k_place_newton<20>, grid, block, 0, c->stream, qs.d, a); break;
+        case 2: hipLaunchKernelGGL(k_place_newton<2>, grid, block, 0, c->stream, d, a); break;
+        case 4: hipLaunchKernelGGL(k_place_newton<4>, grid, block, 0, c->stream, d, a); break;
+        default: hipLaunchKernelGGL(k_place_newton<20>, grid, block, 0, c->stream, d, a); break;
     }
     HIPCHK(&c->err, hipGetLastError());
-    return mark(c, 2, 1);
-}
-
-template <class T>
-int to_host(pu_ctx *c, T *dst, const T *src, size_t n) {
-    if (n) HIPCHK(&c->err, hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-    return PU_OK;
-}
-
-// one re-orientation / restore row of the optimising traversal, as pu_optimise_sweep applies it
-int apply_row(pu_ctx *c, const int32_t *row) {
-    if (row[0] < 0) return PU_OK;
-    int k1, k2, rc;
-    if ((rc = edge_key(c, row[0], row[1], &k1)) || (rc = edge_key(c, row[0], row[2], &k2)))
-        return rc;
-    const double bl[2] = {c->up_len[k1], c->up_len[k2]};
-    return edge_update_ops(c, 1, row, bl);
-}
-
-// An error in mid-walk leaves nodes re-oriented towards the edge the walk stood on: one
-// traversal writes the post-order partials, the lnL and the sitewise lnL back, as the end of a
-// complete walk does (bad rows are refused here; a failed launch may fail the traversal too).
-// The first error is the one reported.
-int abandon_walk(pu_ctx *c, int rc) {
-    const std::string msg = c->err;
-    double lnl;
-    (void)pu_run(c, &lnl, nullptr);
-    return set_err(&c->err, rc, "%s", msg.c_str());
+    return s->timer[2].end(c);
 }
 
 }  // namespace
@@ -756,19 +656,19 @@ int pu_place_edge(pu_ctx *c, int node, int other, double length, int n_query, in
     if ((rc = edge_key(c, node, other, &key)) || (rc = edge_node_src(c, node, &sn)) ||
         (rc = edge_node_src(c, other, &so)))
         return rc;
-    QuerySet qs;
-    if ((rc = upload_queries(c, h, true, qs))) return rc;
+    HostCall hc(c->stream, &c->err);
+    QueryDev d;
+    if ((rc = upload_queries(c, h, true, hc, d))) return rc;
     const size_t Q = (size_t)n_query;
-    DevBuf<double> d_score, d_nt;
-    if ((rc = d_score.alloc(&c->err, Q)) || (rc = d_nt.alloc(&c->err, max_iter ? 5 * Q : 0)))
-        return rc;
-    if ((rc = table_enqueue(c, sn, so, length, h, true)) ||
-        (rc = prescore_enqueue(c, qs, n_query, d_score.p)))
-        return rc;
-    if (max_iter && (rc = newton_enqueue(c, qs, nullptr, n_query, l0, tol, max_iter, d_nt.p)))
-        return rc;
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = place_stamp(c)) || (rc = to_host(c, score_out, d_score.p, Q))) return rc;
+    std::vector<double> nt(max_iter ? 5 * Q : 0);
+    double *d_score = hc.alloc<double>(Q), *d_nt = hc.alloc<double>(nt.size());
+    if (!hc.rc) hc.rc = table_enqueue(c, sn, so, length, h, true);
+    if (!hc.rc) hc.rc = prescore_enqueue(c, d, n_query, d_score);
+    if (!hc.rc && max_iter)
+        hc.rc = newton_enqueue(c, d, nullptr, n_query, l0, tol, max_iter, d_nt);
+    hc.to_host(score_out, d_score, Q);
+    hc.to_host(nt.data(), d_nt, nt.size());
+    if ((rc = hc.finish("pu_place_edge")) || (rc = place_stamp(c))) return rc;
     if (!max_iter) {  // the pre-score alone
         for (size_t i = 0; i < Q; ++i) {
             pendant_out[i] = l0;
@@ -777,8 +677,6 @@ int pu_place_edge(pu_ctx *c, int node, int other, double length, int n_query, in
         }
         return PU_OK;
     }
-    std::vector<double> nt(5 * Q);
-    if ((rc = to_host(c, nt.data(), d_nt.p, 5 * Q))) return rc;
     for (size_t i = 0; i < Q; ++i) {
         pendant_out[i] = nt[5 * i];
         lnl_out[i] = nt[5 * i + 1];
@@ -807,39 +705,36 @@ int pu_place_prescore(pu_ctx *c, int n_rows, const int32_t *rows, int n_query, i
         return set_err(&c->err, PU_E_ARG, "pu_place_prescore: more than 2 n_tips - 3 = %d edges "
                        "in the rows", cap);
     DeviceGuard g(c->device);
-    QuerySet qs;
-    if ((rc = upload_queries(c, h, true, qs))) return rc;
+    HostCall hc(c->stream, &c->err);
+    QueryDev d;
+    if ((rc = upload_queries(c, h, true, hc, d))) return rc;
     const size_t Q = (size_t)n_query;
     // the scores of all edges stay on the device until the walk is over
-    DevBuf<double> d_score;
-    if ((rc = d_score.alloc(&c->err, (size_t)n_edges * Q))) return rc;
-    int count = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if ((rc = apply_row(c, row))) return abandon_walk(c, rc);
-        if (row[3] < 0) continue;
-        const int nod = row[3], par = row[4];
-        int key;
-        NodeSrc sn, so;
-        if ((rc = edge_key(c, nod, par, &key)) || (rc = edge_node_src(c, nod, &sn)) ||
-            (rc = edge_node_src(c, par, &so)))
-            return abandon_walk(c, rc);
-        const double t = c->up_len[key];
-        if ((rc = table_enqueue(c, sn, so, t, h, true)) ||
-            (rc = prescore_enqueue(c, qs, n_query, d_score.p + count * Q)))
-            return abandon_walk(c, rc);
-        edges_out[2 * count] = nod;
-        edges_out[2 * count + 1] = par;
-        lengths_out[count] = t;
-        ++count;
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    if ((rc = place_stamp(c)) || (rc = to_host(c, score_out, d_score.p, count * Q))) return rc;
-    *n_edges_out = count;
-    // every node is back in its post-order orientation by the restore rows' updates; one
-    // traversal rewrites them, the lnL and the sitewise lnL with pu_run's own arithmetic
-    double lnl;
-    return pu_run(c, &lnl, nullptr);
+    double *d_score = hc.alloc<double>((size_t)n_edges * Q);
+    if (hc.rc) return hc.rc;
+    size_t count = 0;
+    return resident_walk(
+        c, n_rows, rows,
+        [&](int, const int32_t *row, int key) {
+            NodeSrc sn, so;
+            int e;
+            if ((e = edge_node_src(c, row[3], &sn)) || (e = edge_node_src(c, row[4], &so)))
+                return e;
+            const double t = c->up_len[key];
+            if ((e = table_enqueue(c, sn, so, t, h, true)) ||
+                (e = prescore_enqueue(c, d, n_query, d_score + count * Q)))
+                return e;
+            edges_out[2 * count] = row[3];
+            edges_out[2 * count + 1] = row[4];
+            lengths_out[count++] = t;
+            return PU_OK;
+        },
+        [&] {
+            hc.to_host(score_out, d_score, count * Q);
+            if (const int e = hc.finish("pu_place_prescore")) return e;
+            *n_edges_out = (int)count;
+            return place_stamp(c);
+        });
 }
 
 int pu_place_refine(pu_ctx *c, int n_rows, const int32_t *rows, int n_query, int64_t n_sites,
@@ -876,57 +771,51 @@ int pu_place_refine(pu_ctx *c, int n_rows, const int32_t *rows, int n_query, int
         return set_err(&c->err, PU_E_ARG, "pu_place_refine: %d edges in the rows, cand_off holds "
                        "%d", walk_edges, n_edges);
     DeviceGuard g(c->device);
-    QuerySet qs;
-    if ((rc = upload_queries(c, h, false, qs))) return rc;
-    DevBuf<int32_t> d_list;
-    DevBuf<double> d_nt;
-    if ((rc = d_list.alloc(&c->err, n_cand)) || (rc = d_nt.alloc(&c->err, 5 * n_cand))) return rc;
-    if (n_cand) {
-        HIPCHK(&c->err, hipMemcpyAsync(d_list.p, cand_query, n_cand * sizeof(int32_t),
-                                       hipMemcpyHostToDevice, c->stream));
-        HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    }
+    HostCall hc(c->stream, &c->err);
+    QueryDev d;
+    if ((rc = upload_queries(c, h, false, hc, d))) return rc;
+    const int32_t *d_list = hc.to_device(cand_query, n_cand);
+    double *d_nt = hc.alloc<double>(5 * n_cand);
+    if (hc.rc) return hc.finish("pu_place_refine");
     int count = 0;
-    for (int r = 0; r < n_rows; ++r) {
-        const int32_t *row = rows + 5 * (size_t)r;
-        if ((rc = apply_row(c, row))) return abandon_walk(c, rc);
-        if (row[3] < 0) continue;
-        const int64_t lo = cand_off[count], n = cand_off[count + 1] - lo;
-        ++count;
-        if (n == 0) continue;
-        int key;
-        NodeSrc sn, so;
-        if ((rc = edge_key(c, row[3], row[4], &key)) || (rc = edge_node_src(c, row[3], &sn)) ||
-            (rc = edge_node_src(c, row[4], &so)))
-            return abandon_walk(c, rc);
-        if ((rc = table_enqueue(c, sn, so, c->up_len[key], h, false)) ||
-            (rc = newton_enqueue(c, qs, d_list.p + lo, (int)n, l0, tol, max_iter,
-                                 d_nt.p + 5 * lo)))
-            return abandon_walk(c, rc);
-    }
-    HIPCHK(&c->err, hipStreamSynchronize(c->stream));
-    std::vector<double> nt(5 * n_cand);
-    if ((rc = place_stamp(c)) || (rc = to_host(c, nt.data(), d_nt.p, 5 * n_cand))) return rc;
-    // candidates of edges past the walk's last keep NaN
-    for (size_t i = 0; i < n_cand; ++i) {
-        const bool done = i < (size_t)cand_off[count];
-        pendant_out[i] = done ? nt[5 * i] : NAN;
-        lnl_out[i] = done ? nt[5 * i + 1] : NAN;
-        derivs_out[2 * i] = done ? nt[5 * i + 2] : NAN;
-        derivs_out[2 * i + 1] = done ? nt[5 * i + 3] : NAN;
-        iters_out[i] = done ? (int32_t)nt[5 * i + 4] : -1;
-    }
-    double lnl;
-    return pu_run(c, &lnl, nullptr);
+    return resident_walk(
+        c, n_rows, rows,
+        [&](int, const int32_t *row, int key) {
+            const int64_t lo = cand_off[count], n = cand_off[count + 1] - lo;
+            ++count;
+            if (n == 0) return PU_OK;
+            NodeSrc sn, so;
+            int e;
+            if ((e = edge_node_src(c, row[3], &sn)) || (e = edge_node_src(c, row[4], &so)) ||
+                (e = table_enqueue(c, sn, so, c->up_len[key], h, false)))
+                return e;
+            return newton_enqueue(c, d, d_list + lo, (int)n, l0, tol, max_iter, d_nt + 5 * lo);
+        },
+        [&] {
+            std::vector<double> nt(5 * n_cand);
+            hc.to_host(nt.data(), d_nt, nt.size());
+            int e;
+            if ((e = hc.finish("pu_place_refine")) || (e = place_stamp(c))) return e;
+            // candidates of edges past the walk's last keep NaN
+            for (size_t i = 0; i < n_cand; ++i) {
+                const bool done = i < (size_t)cand_off[count];
+                pendant_out[i] = done ? nt[5 * i] : NAN;
+                lnl_out[i] = done ? nt[5 * i + 1] : NAN;
+                derivs_out[2 * i] = done ? nt[5 * i + 2] : NAN;
+                derivs_out[2 * i + 1] = done ? nt[5 * i + 3] : NAN;
+                iters_out[i] = done ? (int32_t)nt[5 * i + 4] : -1;
+            }
+            return PU_OK;
+        });
 }
 
 int pu_place_kernel_ms(pu_ctx *c, double *table_ms, double *prescore_ms, double *newton_ms) {
     if (!c || !table_ms || !prescore_ms || !newton_ms)
         return set_err(c ? &c->err : nullptr, PU_E_ARG, "null argument");
     const PlaceState *s = c->place;
-    *table_ms = s ? (double)s->ms[0] : 0.0;
-    *prescore_ms = s ? (double)s->ms[1] : 0.0;
-    *newton_ms = s ? (double)s->ms[2] : 0.0;
+    *table_ms = s ? (double)s->timer[0].ms : 0.0;
+    *prescore_ms = s ? (double)s->timer[1].ms : 0.0;
+    *newton_ms = s ? (double)s->timer[2].ms : 0.0;
     return PU_OK;
 }
 

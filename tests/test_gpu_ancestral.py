@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import ancestral_reference as R
+import walk_errors as W
 
 from phylo_utils_amd import TreeModel, ancestral
 from phylo_utils_amd import _native as N
@@ -226,3 +227,19 @@ def test_refusals():
     for call in (tm.ancestral_states, tm.site_rates):
         with pytest.raises(ValueError, match="reversible"):
             call()
+
+
+def test_an_error_in_mid_walk_puts_the_context_back():
+    """pu_ancestral_sweep on rows whose last edge names a PAR that is not NOD's neighbour
+    (walk_errors.py): PU_E_ARG, and the lnL, sitewise lnL and partials are pu_run's again."""
+    prob = R.problem("dna-8x65-C3")
+    tm = _tm(prob)
+    tm.likelihood()
+    bad = W.rows_with_a_bad_last_edge(tm)
+    before = W.snapshot(tm)
+    n, S = len(tm.names) - 2, prob["codes"].shape[1]
+    nodes, st8, pr, lnl, cnt = (np.zeros(n, dtype=np.int32), np.zeros((n, S), dtype=np.uint8),
+                                np.zeros((n, S)), np.zeros(n), ctypes.c_int())
+    rc = N.lib().pu_ancestral_sweep(tm._ctx, len(bad), N.ptr(bad), N.ptr(nodes), N.ptr(st8),
+                                    N.ptr(pr), None, N.ptr(lnl), ctypes.byref(cnt))
+    W.assert_refused_and_put_back(tm, before, rc)

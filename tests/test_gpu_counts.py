@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import counts_reference as R
+import walk_errors as W
 
 from phylo_utils_amd import TreeModel, gradient, modelfit
 from phylo_utils_amd import _native as N
@@ -313,3 +314,19 @@ def test_cli_fit_end_to_end(tmp_path, capsys):
     assert capsys.readouterr().out == plain
     print("phy --fit: lnL %.6f -> %.6f, read back %.6f, %s" % (lnl_of(plain), lnl_fit, back,
                                                                 lines[0]))
+
+
+def test_an_error_in_mid_walk_puts_the_context_back():
+    """pu_counts_sweep on rows whose last edge names a PAR that is not NOD's neighbour
+    (walk_errors.py): PU_E_ARG, and the lnL, sitewise lnL and partials are pu_run's again."""
+    prob = _problem("dna-8x65-C3")
+    tm = _tm(prob)
+    tm.likelihood()
+    bad = W.rows_with_a_bad_last_edge(tm)
+    before = W.snapshot(tm)
+    n, C, K = 2 * len(tm.names) - 3, prob["rm"].ncat, 4
+    edges, lens, counts, lnl, cnt = (np.zeros((n, 2), dtype=np.int32), np.zeros(n),
+                                     np.zeros((n, C, K, K)), np.zeros(n), ctypes.c_int())
+    rc = N.lib().pu_counts_sweep(tm._ctx, len(bad), N.ptr(bad), N.ptr(edges), N.ptr(lens),
+                                 N.ptr(counts), N.ptr(lnl), ctypes.byref(cnt))
+    W.assert_refused_and_put_back(tm, before, rc)

@@ -13,6 +13,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import walk_errors as W
+
 from phylo_utils_amd import TreeModel
 from phylo_utils_amd import _native as N
 from phylo_utils_amd import substitution_models as SM
@@ -575,3 +577,24 @@ def test_device_newton_falls_back_to_the_host_loop(monkeypatch):
     lnl0 = tm.likelihood()
     assert tm.optimise_branch_lengths() > lnl0
     assert _newton_stats(tm) == (0, 0)
+
+
+def test_an_error_in_mid_sweep_puts_the_context_back():
+    """pu_optimise_sweep with max_iter = 0 (no length moves) on rows whose last edge names a PAR
+    that is not NOD's neighbour (walk_errors.py): PU_E_ARG, and the lnL, sitewise lnL and
+    partials are pu_run's again."""
+    m, rm = SM.GTR(CFG2_GTR_RATES, CFG2_FREQS), GammaRateModel(3, 0.5)
+    tree, names, st = make_problem(8, 65, m, rm.rates, seed=2)
+    tm = TreeModel(device=0, keep_partials=True)
+    tm.set_alignment_codes(st.astype(np.uint8), np.eye(4), names)
+    tm.set_substitution_model(m)
+    tm.set_rate_model(rm)
+    tm.set_tree(tree)
+    tm.initialise()
+    tm.likelihood()
+    bad = W.rows_with_a_bad_last_edge(tm)
+    before = W.snapshot(tm)
+    lnl, n_it = ctypes.c_double(), ctypes.c_int()
+    rc = N.lib().pu_optimise_sweep(tm._ctx, len(bad), N.ptr(bad), 1e-8, 0, ctypes.byref(lnl),
+                                   ctypes.byref(n_it))
+    W.assert_refused_and_put_back(tm, before, rc)

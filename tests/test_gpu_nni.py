@@ -9,6 +9,7 @@ import pytest
 
 import nni_reference as R
 import twostate as T
+import walk_errors as W
 from test_cli import _write_case
 
 from phylo_utils_amd import TreeModel, phy
@@ -303,3 +304,23 @@ def test_cli_nni(tmp_path, capsys):
     assert len(prepare_tree(out.read_text()).leaf_nodes()) == 9
     assert phy.main(["-t", nw, "-s", fa, "-m", spec, "--nni", "2"]) == 0
     assert np.isfinite(float(capsys.readouterr().out.split("=")[1]))
+
+
+def test_an_error_in_mid_walk_puts_the_context_back():
+    """pu_nni_sweep, then pu_branch_support, on rows whose last edge names a PAR that is not
+    NOD's neighbour (walk_errors.py): PU_E_ARG from both, and the lnL, sitewise lnL and partials
+    are pu_run's again."""
+    tm, _, _, _ = _setup(*CASES["dna-S65-C3"][:4], seed=2)
+    tm.likelihood()
+    bad = W.rows_with_a_bad_last_edge(tm)
+    before = W.snapshot(tm)
+    n, n_rep = len(tm.names) - 3, 10
+    scores, quartets, cnt = np.zeros((n, 3, 4)), np.zeros((n, 6), dtype=np.int32), ctypes.c_int()
+    rc = N.lib().pu_nni_sweep(tm._ctx, len(bad), N.ptr(bad), 1e-8, 50, N.ptr(scores),
+                              N.ptr(quartets), ctypes.byref(cnt))
+    W.assert_refused_and_put_back(tm, before, rc)
+    sup = np.zeros((n, 4))
+    rc = N.lib().pu_branch_support(tm._ctx, len(bad), N.ptr(bad), 1e-8, 50, 7, 0, n_rep, 0.1,
+                                   N.ptr(scores), N.ptr(quartets), N.ptr(sup), None,
+                                   ctypes.byref(cnt))
+    W.assert_refused_and_put_back(tm, before, rc)
