@@ -445,6 +445,51 @@ int pu_place_refine(pu_ctx *ctx, int n_rows, const int32_t *rows, int n_query, i
 /* HIP-event times (ms) of the last k_place_table, k_place_prescore and k_place_newton launches
  * made while pu_ctx_profile was on. */
 int pu_place_kernel_ms(pu_ctx *ctx, double *table_ms, double *prescore_ms, double *newton_ms);
+/* ---- subtree pruning and regrafting (the reference has no tree search) -------- */
+/* Pruning the subtree on n's side of edge (n, o), o internal, dissolves o: its other neighbours
+ * are joined by one edge of the sum of their two lengths, which leaves the rest tree R.  With A,
+ * B the directed vectors of R at the ends of an edge of length t (neither holds the subtree), S
+ * the vector at n pointing at o, sA, sB, sS their scalers and l = len(n, o):
+ *   g_pc     = sum_i pi_i [P_c(t/2) A_pc](i) [P_c(t/2) B_pc](i) [P_c(l) S_pc](i)
+ *   sigma_pc = sA_pc + sB_pc + sS_pc,  m_p = max_c sigma_pc (categories with g_pc > 0)
+ *   score    = sum_p w_p (m_p + log sum_c w_c e^{sigma_pc - m_p} g_pc)
+ * the lnL of the tree with the subtree regrafted at the edge's midpoint, every other length
+ * unchanged (pulley principle).  A pattern of weight 0 adds nothing; one of non-zero weight and
+ * a non-positive inner sum makes the score -inf.  A score is bitwise reproducible and depends
+ * only on (A, B, S, t, l) and the pattern count.
+ * Common refusals, before any launch: PU_KEEP_PARTIALS contexts on the device eigen-system (a
+ * reversible model) without an ascertainment correction (else PU_E_STATE); PU_E_ARG: more
+ * categories than pu_regraft_max_cat, a node outside [0, n_nodes), a repeated node among the
+ * three scored, a length that is not finite or not > 0. */
+/* The largest category count k_regraft takes for n_states = 2, 4 or 20: its LDS use of one
+ * workgroup against the 160 KiB of a CU, and no more than a context holds; PU_E_ARG for other
+ * n_states.  Host only. */
+int pu_regraft_max_cat(int n_states);
+/* One score on the CURRENT partials of nodes a, b (the edge's ends) and s (the subtree), tips
+ * or kept internal nodes, at edge length t and pendant length l: *score_out.  Changes nothing
+ * in the context. */
+int pu_regraft_edge(pu_ctx *ctx, int a, int b, int s, double t, double l, double *score_out);
+/* One pass over the optimising traversal (rows[n_rows][5], as pu_counts_sweep); while it stands
+ * on the edge of row r it runs the inner rows inner_off[r] .. inner_off[r + 1] (inner_off
+ * [n_rows + 1] starts at 0 and does not decrease; a row that names no edge has none).  Inner row
+ * i is inner_rows[i][6] = (x0, x1, x2, A, B, S) with inner_len[i][4] = (len1, len2, t, l): if
+ * x0 >= 0, node x0 is updated in place from x1 at len1 and x2 at len2 (pu_update_partials: a
+ * re-orientation or a restore at explicit lengths); then, if A >= 0, scores_out[i] = the score
+ * of (A, B, S, t, l); a row with A < 0 gets NaN.  The library knows nothing about trees: the
+ * caller's rows of one edge must end with the restores that put back every node they
+ * re-oriented.  Before the pass every kept partial is rewritten by the update kernel from its
+ * children, so that a restore reproduces the bits it replaces.  The scores stay on the device
+ * during the pass and are copied once.  PU_E_ARG also for inner_off[0] != 0 or decreasing,
+ * inner rows on a row without an edge, and x0 equal to A, B or S of a scoring row; all rows are
+ * checked before any launch.  The pass ends with a full traversal (its lnL to *lnl_out,
+ * nullable), so the context's partials, lnL and sitewise lnL are bitwise those of pu_run before
+ * the call.  An error in mid-pass (an update of a tip, a failed launch) runs that traversal too
+ * before the first error is returned. */
+int pu_spr_sweep(pu_ctx *ctx, int n_rows, const int32_t *rows, const int64_t *inner_off,
+                 const int32_t *inner_rows, const double *inner_len, double *scores_out,
+                 double *lnl_out);
+/* HIP-event time (ms) of the last k_regraft launch made while pu_ctx_profile was on. */
+int pu_spr_kernel_ms(pu_ctx *ctx, double *regraft_ms);
 /* Current lengths in pu_set_schedule's layout: brlens_out[n_ops][2], root length. */
 int pu_get_branch_lengths(pu_ctx *ctx, double *brlens_out, double *root_len_out);
 

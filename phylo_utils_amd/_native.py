@@ -113,6 +113,10 @@ SIGNATURES = {
     "pu_place_refine": (_c_int, [_P, _c_int, _P, _c_int, _c_i64, _P, _P, _P, _c_int, _P, _c_dbl,
                                  _c_dbl, _c_int, _c_int, _P, _P, _P, _P, _P, _P]),
     "pu_place_kernel_ms": (_c_int, [_P, _P, _P, _P]),
+    "pu_regraft_max_cat": (_c_int, [_c_int]),
+    "pu_regraft_edge": (_c_int, [_P, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _P]),
+    "pu_spr_sweep": (_c_int, [_P, _c_int, _P, _P, _P, _P, _P, _P]),
+    "pu_spr_kernel_ms": (_c_int, [_P, _P]),
     "pu_get_branch_lengths": (_c_int, [_P, _P, _P]),
     "pu_lnl_branch": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pu_lnl_branch_derivs": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _P, _P, _P, _P, _P, _P,

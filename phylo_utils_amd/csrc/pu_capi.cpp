@@ -346,6 +346,7 @@ void pu_ctx_destroy(pu_ctx *c) {
     edge_free(c);
     sim_free(c);
     place_free(c);
+    spr_free(c);
     dfree(c->d_tips);
     if (c->tip_store) {  // shared tips: the last holder frees them
         c->d_codes = nullptr;

@@ -91,6 +91,7 @@ struct TipStore {
 
 struct SimState;  // pu_simulate.hip: the simulator's device buffers of a context
 struct PlaceState;  // pu_place.hip: the placement tables of a context
+struct SprState;  // pu_spr.hip: the regraft buffers of a context
 
 // The HIP-event time of the last launch of one kernel while the context is profiling
 // (pu_ctx_profile): begin and end are recorded round the launch, on the context's stream, and
@@ -262,6 +263,9 @@ struct pu_ctx {
     pu::SimState *sim = nullptr;
     // placement (pu_place.hip): allocated at the first pu_place_* call
     pu::PlaceState *place = nullptr;
+    // subtree pruning and regrafting (pu_spr.hip): allocated at the first pu_regraft_edge /
+    // pu_spr_sweep call
+    pu::SprState *spr = nullptr;
 
     // profiling: event triples per recorded run
     bool profile = false;
@@ -303,6 +307,8 @@ void edge_free(pu_ctx *c);
 void sim_free(pu_ctx *c);
 // pu_place.hip: release the placement buffers of a context
 void place_free(pu_ctx *c);
+// pu_spr.hip: release the regraft buffers of a context
+void spr_free(pu_ctx *c);
 // enqueue the ascertainment-bias correction of site_lnl and *lnl (no-op when off)
 int enqueue_ascbias(pu_ctx *c, double *lnl);
 // stateless seam calls (pu_clv, pu_lnl_node, pu_lnl_branch*): one scratch buffer and stream

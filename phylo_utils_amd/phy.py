@@ -35,6 +35,11 @@ replicates (``phylo_utils_amd.bootstrap``);
 ``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
 interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
 rounds, default 50); ``-o`` then receives the final Newick;
+``--spr [ROUNDS]`` (after ``-t`` or ``--nj``, and after ``--nni`` when both are given) improves the
+topology by subtree pruning and regrafting on the GPU before the ``lnL = `` line
+(``phylo_utils_amd.spr``, at most ROUNDS rounds, default 50; ``--spr-radius R`` scores only the
+regraft edges within R edges of the pruned subtree's old place, default: all); ``-o`` then
+receives the final Newick;
 ``--support [R]`` (after ``-t`` or ``--nj``, and after ``--nni`` when given) labels every internal
 edge of the final tree with ``SH-aLRT/aBayes`` -- percent with one decimal over R RELL replicates
 (default 1000, the seed of ``--seed``) and probability with three (``phylo_utils_amd.support``)
@@ -186,6 +191,13 @@ def parse_cli(argv=None):
     ap.add_argument("--nni", type=int, nargs="?", const=50, default=None, metavar="ROUNDS",
                     help="after -t or --nj: nearest-neighbour-interchange search (at most ROUNDS "
                          "rounds, default 50) before the lnL line; -o receives the final Newick")
+    ap.add_argument("--spr", type=int, nargs="?", const=50, default=None, metavar="ROUNDS",
+                    help="after -t or --nj (and --nni): subtree-pruning-and-regrafting search (at "
+                         "most ROUNDS rounds, default 50) before the lnL line; -o receives the "
+                         "final Newick")
+    ap.add_argument("--spr-radius", type=int, default=None, metavar="R", dest="spr_radius",
+                    help="with --spr: score only the regraft edges within R edges of the pruned "
+                         "subtree's old place (default: every edge)")
     ap.add_argument("--support", type=int, nargs="?", const=1000, default=None, metavar="R",
                     help="after -t or --nj (and --nni): label the internal edges of the final "
                          "tree with SH-aLRT/aBayes supports over R RELL replicates (default "
@@ -244,6 +256,17 @@ def validate_args(args):
             raise ValueError("--nni excludes --simulate and --distances")
         if args.nni < 0:
             raise ValueError("--nni needs a non-negative number of rounds")
+    if getattr(args, "spr", None) is not None or getattr(args, "spr_radius", None) is not None:
+        if getattr(args, "spr", None) is None:
+            raise ValueError("--spr-radius needs --spr")
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--spr excludes --simulate and --distances")
+        if getattr(args, "ascertainment", None):
+            raise ValueError("--spr with --ascertainment is not implemented")
+        if args.spr < 0:
+            raise ValueError("--spr needs a non-negative number of rounds")
+        if getattr(args, "spr_radius", None) is not None and args.spr_radius < 1:
+            raise ValueError("--spr-radius needs a radius of at least 1")
     if getattr(args, "support", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--support excludes --simulate and --distances")
@@ -321,6 +344,12 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
+    if getattr(args, "spr", None) is not None:
+        tree, _, _ = tm.spr_search(radius=getattr(args, "spr_radius", None), max_rounds=args.spr,
+                                   sweeps=max(args.optimise, 1), method=args.optimiser)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
     fitted = None
     if getattr(args, "fit", None) is not None:
         from . import modelfit
@@ -347,7 +376,8 @@ def run(args, out=None):
     if getattr(args, "support", None) is not None:
         from .support import label_tree, support_label
         from .tree import with_lengths
-        if not args.optimise and getattr(args, "nni", None) is None:
+        if not args.optimise and getattr(args, "nni", None) is None and \
+                getattr(args, "spr", None) is None:
             tm.optimise_branch_lengths(sweeps=1, method=args.optimiser)
         quartets, _, sup = tm.branch_support(n_replicates=args.support, seed=args.seed)
         tree = label_tree(with_lengths(tm.tree, tm.traversal.brlens), quartets,

@@ -419,3 +419,161 @@ def with_lengths(tree, brlens):
         else:
             n.length = float(bl[(i, tr.node_dict[n.parent])])
     return t
+
+
+# ---------------------------------------------------------------- subtree pruning and regrafting
+# Host helpers of the SPR search (phylo_utils_amd.spr).  Nodes are named by their
+# Traversal index on prepare_tree(tree), the tree is taken as unrooted: the two ends of the root
+# edge are ordinary internal nodes joined by an edge, the seed is not a node.  A prune candidate
+# is a directed edge (n, o): the subtree on n's side is cut, o -- internal, with other neighbours
+# x and y -- is dissolved and x, y are joined by one edge of length len(x, o) + len(y, o), which
+# leaves the rest tree R; R must keep at least two edges (x and y are not both leaves).  A move
+# (n, o, u, v) regrafts the subtree at the midpoint of R's edge (u, v) on its pendant length
+# len(n, o); (u, v) = (x, y) is the merged edge, distance 0, an edge sharing a node with it has
+# distance 1 (the NNI topologies), and so on outward.
+
+def _neighbours(tr):
+    """{node: {neighbour: length}} of the unrooted tree of a Traversal."""
+    adj = {i: {} for i in range(tr.n_nodes)}
+    for (a, b), t in tr.brlens.items():
+        adj[a][b] = float(t)
+        adj[b][a] = float(t)
+    return adj
+
+
+def _spr_ends(adj, n, o):
+    """(x, y) of candidate (n, o), or None where it is none."""
+    if o not in adj.get(n, ()) or len(adj[o]) != 3:
+        return None
+    x, y = [z for z in adj[o] if z != n]
+    if len(adj[x]) == 1 and len(adj[y]) == 1:
+        return None
+    return x, y
+
+
+def spr_candidates(tree):
+    """The prune candidates [(n, o)] of `tree` in optimising-traversal order: both directions
+    of every edge (NOD, PAR) -- (NOD, PAR), then (PAR, NOD) -- wherever the dissolved end is
+    internal and the rest tree keeps at least two edges."""
+    tr = Traversal(prepare_tree(tree))
+    adj = _neighbours(tr)
+    out = []
+    for row in tr.optimising_traversal:
+        nod, par = int(row[3]), int(row[4])
+        if nod < 0:
+            continue
+        for n, o in ((nod, par), (par, nod)):
+            if _spr_ends(adj, n, o) is not None:
+                out.append((n, o))
+    return out
+
+
+def spr_rows(traversal, radius=None):
+    """The rows of one scoring pass (pu_spr_sweep) over `traversal`: (rows int32 [R][5] = the
+    optimising traversal, inner_off int64 [R + 1], inner_rows int32 [I][6] = (x0, x1, x2, A, B,
+    S), inner_len [I][4] = (len1, len2, t, l), moves int32 [I][5] = (n, o, u, v, distance)).
+
+    While the walk stands on edge (NOD, PAR) every node's vector points at that edge, so for the
+    candidates (NOD, PAR) and (PAR, NOD) every vector of R points at the merged edge: its two
+    ends score distance 0 as they are.  From there an iterative depth-first search of R (a
+    1000-taxon caterpillar is deeper than Python's recursion limit) re-orients a node u towards
+    a far neighbour v from its other far neighbour and its near one (an update row, A = -1),
+    scores edge (v, u) (a scoring row, x0 = -1: A = v, B = u, S = n), descends into v, does the
+    same for the other far neighbour, and on the way out restores u from its two far neighbours
+    (an update row).  `radius`: only edges of distance <= radius (None: every edge of R).  An
+    update row has u = v = distance = -1 in `moves`."""
+    tr = traversal
+    adj = _neighbours(tr)
+    rows = np.ascontiguousarray(tr.optimising_traversal, dtype=np.int32).reshape(-1, 5)
+    off, inner, lens, moves = [0], [], [], []
+    limit = None if radius is None else int(radius)
+
+    def update(n, o, u, a, la, b, lb):
+        inner.append((u, a, b, -1, -1, -1))
+        lens.append((la, lb, 0.0, 0.0))
+        moves.append((n, o, -1, -1, -1))
+
+    def score(n, o, a, b, t, l, dist):
+        inner.append((-1, -1, -1, a, b, n))
+        lens.append((0.0, 0.0, t, l))
+        moves.append((n, o, a, b, dist))
+
+    for row in rows:
+        nod, par = int(row[3]), int(row[4])
+        for n, o in (((nod, par), (par, nod)) if nod >= 0 else ()):
+            ends = _spr_ends(adj, n, o)
+            if ends is None:
+                continue
+            x, y = ends
+            l, merged = adj[n][o], adj[o][x] + adj[o][y]
+            score(n, o, x, y, merged, l, 0)
+            if limit is not None and limit < 1:
+                continue
+            for start, other in ((x, y), (y, x)):
+                # (u, near, length to near, far neighbours, distance of u's far edges, stage)
+                stack = [[start, other, merged, [z for z in adj[start] if z != o], 1, 0]]
+                while stack:
+                    top = stack[-1]
+                    u, near, t_near, far, dist, stage = top
+                    if len(far) != 2 or stage == 2:  # a leaf of R, or both sides done
+                        if len(far) == 2:
+                            update(n, o, u, far[0], adj[u][far[0]], far[1], adj[u][far[1]])
+                        stack.pop()
+                        continue
+                    v, w = far[stage], far[1 - stage]
+                    top[5] = stage + 1
+                    update(n, o, u, w, adj[u][w], near, t_near)
+                    score(n, o, v, u, adj[u][v], l, dist)
+                    if limit is None or dist < limit:
+                        stack.append([v, u, adj[u][v], [z for z in adj[v] if z != u], dist + 1, 0])
+        off.append(len(inner))
+    return (rows, np.array(off, dtype=np.int64),
+            np.array(inner, dtype=np.int32).reshape(-1, 6),
+            np.array(lens, dtype=np.float64).reshape(-1, 4),
+            np.array(moves, dtype=np.int32).reshape(-1, 5))
+
+
+def apply_spr(tree, n, o, u, v):
+    """A new Tree: the subtree on n's side of edge (n, o) of prepare_tree(tree) cut out, the
+    dissolved o's other neighbours x, y joined by one edge of length len(x, o) + len(y, o), edge
+    (u, v) of the rest tree -- (x, y), in either order, names the merged edge -- split into two
+    halves at a new node, and the subtree hung from that node at its old length len(n, o).  All
+    other lengths are kept.  The result is rooted on the pendant edge; internal labels are
+    dropped (a support label belongs to a split of the old tree)."""
+    tr = Traversal(prepare_tree(tree))
+    adj = _neighbours(tr)
+    n, o, u, v = int(n), int(o), int(u), int(v)
+    ends = _spr_ends(adj, n, o) if n in adj else None
+    if ends is None:
+        raise ValueError("(%d, %d) is no prune candidate: an edge whose end %d is internal, with "
+                         "at least two edges left" % (n, o, o))
+    x, y = ends
+    l = adj[n][o]
+    merged = adj[o][x] + adj[o][y]
+    for z in (x, y):
+        del adj[z][o]
+    adj[o] = {n: l}
+    adj[x][y] = adj[y][x] = merged
+    side, todo = {n}, [n]  # n's subtree: what is reached from n without passing o
+    while todo:
+        for z in adj[todo.pop()]:
+            if z != o and z not in side:
+                side.add(z)
+                todo.append(z)
+    if u not in adj or v not in adj.get(u, ()) or o in (u, v) or u in side or v in side:
+        raise ValueError("(%d, %d) is no edge of the rest tree of (%d, %d)" % (u, v, n, o))
+    t = adj[u].pop(v)
+    del adj[v][u]
+    for z in (u, v):
+        adj[o][z] = adj[z][o] = 0.5 * t
+    label = {i: node.label for node, i in tr.node_dict.items() if node.is_leaf()}
+    seed = Node()
+    stack = []
+    for child, parent, length in ((n, o, l), (o, n, 0.0)):
+        stack.append((child, parent, seed.add(Node(label.get(child), length))))
+    while stack:
+        i, came, node = stack.pop()
+        for z in sorted(adj[i]):
+            if z != came:
+                stack.append((z, i, node.add(Node(label.get(z), adj[i][z]))))
+    return Tree(seed)

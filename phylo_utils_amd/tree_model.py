@@ -605,6 +605,20 @@ class TreeModel(object):
         from . import nni
         return nni.nni_search(self, max_rounds, min_gain, sweeps, tol, method)
 
+    def spr_scores(self, radius=None):
+        """The lnL of every subtree-pruning-and-regrafting move within `radius` edges (None: all)
+        at unchanged lengths, in one pass of the optimising traversal (``spr.spr_scores``,
+        pu_spr_sweep): (moves [n][5] = n, o, u, v, distance; scores [n])."""
+        from . import spr
+        return spr.spr_scores(self, radius)
+
+    def spr_search(self, radius=None, max_rounds=50, keep=5, min_gain=1e-3, sweeps=1, tol=1e-8,
+                   method="newton"):
+        """Subtree-pruning-and-regrafting search from the current tree (``spr.spr_search``):
+        returns (tree, lnL, history); the model ends on that tree with its lengths optimised."""
+        from . import spr
+        return spr.spr_search(self, radius, max_rounds, keep, min_gain, sweeps, tol, method)
+
     def quartet_site_lnl(self, nodes, lens, t=None):
         """The unweighted per-pattern lnL of the three arrangements of four nodes, and their
         {lnL, d1, d2} (``support.quartet_site_lnl``, pu_quartet_site_lnl): (site [3][S],
