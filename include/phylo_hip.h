@@ -305,6 +305,20 @@ int pu_branch_support(pu_ctx *ctx, int n_rows, const int32_t *rows, double tol, 
                       uint64_t seed, int64_t first_rep, int n_rep, double epsilon,
                       double *scores_out, int32_t *quartets_out, double *support_out,
                       double *rell_out, int *n_scored_out);
+/* ---- impossible patterns on the resident-partials calls ---------------------
+ * A pattern that no state explains (a dense tip row of zeros) has Z = 0 in every kernel that
+ * mixes the categories (pu_edge_lnl, the quartet, ancestral, counts, placement and regraft
+ * kernels).  What they write there:
+ *   - the pattern's own lnL (sitewise lnL, pu_quartet_site_lnl) is -inf;
+ *   - a lnL summed over the patterns is -inf if the pattern's weight is not 0, and does not see
+ *     the pattern if it is 0: weight 0 adds exactly 0, never 0 x -inf (the traversal's own lnL,
+ *     pu_run / pu_synchronize, included);
+ *   - the per-pattern quotients post, map_prob, cat_post and mean_rate are 0 / 0 = NaN at that
+ *     pattern, whatever its weight, and map_state there is unspecified; every other pattern is
+ *     unaffected;
+ *   - the count matrices take coef = pw w_c e^{..} / Z: exactly 0 for weight 0, NaN otherwise
+ *     (gradient.edge_counts refuses a lnL that is not finite);
+ *   - placement and regraft scores are sums over patterns and follow the second rule. */
 /* ---- marginal ancestral states and site-rate posteriors -------------------- */
 /* The largest category count the ancestral kernel takes for n_states = 2, 4 or 20: its LDS use
  * of one workgroup against the 160 KiB of a CU, and no more than a context holds (64, 50, 10);

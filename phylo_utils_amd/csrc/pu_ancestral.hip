@@ -104,7 +104,8 @@ __global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, Anc
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        lds[L.P + idx] = acc;
+        // an invariable category (rate 0): P = I itself, as the traversal builds it
+        lds[L.P + idx] = rt[c] == 0.0 ? (i == j ? 1.0 : 0.0) : acc;
     }
     __syncthreads();
 

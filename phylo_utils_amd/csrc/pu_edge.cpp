@@ -198,7 +198,8 @@ void host_p_mats(const pu_ctx *c, int n_mat, const double *ts, const int *ord, d
                 for (int j = 0; j < K; ++j) {
                     double acc = 0.0;
                     for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-                    P[i * K + j] = acc;
+                    // an invariable category (rate 0): P = I itself, as build_p
+                    P[i * K + j] = (r == 0.0 && ord[m] == 0) ? (i == j ? 1.0 : 0.0) : acc;
                 }
         }
 }

@@ -134,7 +134,10 @@ __device__ void build_p(const EdgeArgs &a, double *lds, const EdgeLds &L, int n_
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        P[idx] = acc;
+        // an invariable category (rate 0): P = I itself, as the traversal builds it (DESIGN
+        // 4.21); its derivatives are exactly 0 already (x = 0)
+        const int c = mc % C, m = mc / C;
+        P[idx] = (rt[c] == 0.0 && ord[m] == 0) ? (i == j ? 1.0 : 0.0) : acc;
     }
     lds_barrier();
 }

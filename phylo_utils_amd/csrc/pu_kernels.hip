@@ -210,6 +210,10 @@ __device__ __forceinline__ void pmatrix_lane(const AR &a, const int e) {
     const int m = e / K, i = e - m * K;
     const int sd = m / a.C, c = m - sd * a.C;
     const double t = a.brlens[sd] * a.rates[c];
+    // an invariable category (rate 0) has P = I itself, not U U^-1 = I plus rounding of either
+    // sign: its vectors are then exact products of tip rows, exactly 0 at a variable pattern,
+    // and the masked mixes downstream drop it there
+    const bool ident = a.rates[c] == 0.0;
     // the eigen-system and the code table are wave-uniform: scalar loads, which a store does
     // not hold up (vector loads after the P stores waited for them, 10 us per batch launch)
     const cptr<double> ev = as_const(a.evals), U = as_const(a.evecs), V = as_const(a.ivecs);
@@ -220,7 +224,7 @@ __device__ __forceinline__ void pmatrix_lane(const AR &a, const int e) {
 #pragma unroll
         for (int k = 0; k < K; ++k)
             acc = fma(U[i * K + k] * exp(ev[k] * t), V[k * K + j], acc);
-        p[j] = acc;
+        p[j] = ident ? (i == j ? 1.0 : 0.0) : acc;
     }
     double *P = a.P + (size_t)e * K;
 #pragma unroll
@@ -864,7 +868,7 @@ __device__ __forceinline__ void prune_tree(const TA &a, const int bid0) {
         if (live && cat == 0 && site < a.S) {
             const double l = lse_strided(lnl_x + wave * 64 + lane, C, 64);
             a.site_lnl[site] = l;
-            contrib = pw_site * l;
+            contrib = pw_site != 0.0 ? pw_site * l : 0.0;  // weight 0 adds 0, never 0 x -inf
         }
         const double t = block_sum_256(contrib, lnl_x + kBlock);
         // single-tree DNA launches only (K = 2 builds would take a stack frame; a batch sums
@@ -1549,7 +1553,8 @@ __global__ void __launch_bounds__(kBlock, 3) k_prune_mfma(TraverseArgs a) {
     if (threadIdx.x < kTile && st < a.S) {
         const double l = lse_strided(a.cat_lnl + st, C, (int64_t)n_tiles * kTile);
         a.site_lnl[st] = l;
-        contrib = a.pattern_w[st] * l;
+        const double pw = a.pattern_w[st];
+        contrib = pw != 0.0 ? pw * l : 0.0;  // weight 0 adds 0, never 0 x -inf
     }
     const double t = block_sum_256(contrib, red);
     if (!a.lnl_out) {  // k_reduce adds the tiles
@@ -1631,8 +1636,10 @@ __global__ void __launch_bounds__(kBlock) k_pmatrix_aa(PmatArgs a) {
             acc0 = fma(evx[r * K + k], b, acc0);
             if (two) acc1 = fma(evx[(r + 12) * K + k], b, acc1);
         }
-        pm[r * K + j] = acc0;
-        if (two) pm[(r + 12) * K + j] = acc1;
+        // an invariable category (rate 0): P = I itself (pmatrix_lane)
+        const bool ident = a.rates[c] == 0.0;
+        pm[r * K + j] = ident ? (r == j ? 1.0 : 0.0) : acc0;
+        if (two) pm[(r + 12) * K + j] = ident ? (r + 12 == j ? 1.0 : 0.0) : acc1;
     }
     __syncthreads();
     // [k-step q][lane][2]: .x = P[lane & 15][4q + (lane >> 4)] (the 16x16x4 rows),
@@ -1676,7 +1683,8 @@ __global__ void __launch_bounds__(kBlock)
     if (s < S) {
         const double l = lse_strided(cat_lnl + s, C, S_pad);
         site_lnl[s] = l;
-        contrib = pattern_w[s] * l;
+        const double pw = pattern_w[s];
+        contrib = pw != 0.0 ? pw * l : 0.0;  // weight 0 adds 0, never 0 x -inf
     }
     const double t = block_sum_256(contrib, red);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = t;

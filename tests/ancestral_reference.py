@@ -99,12 +99,16 @@ def posterior(orc, P, S, n, o, t, e):
     g = e["freqs"][None, None, :] * P[n] * np.einsum("cij,scj->sci", pm, P[o])
     F = g.sum(axis=2)
     sigma = S[n] + S[o]
-    m = sigma.max(axis=1)
-    we = e["weights"][None, :] * np.exp(sigma - m[:, None])
-    Z = (we * F).sum(axis=1)
-    q = (we[:, :, None] * g).sum(axis=1) / Z[:, None]
-    r = we * F / Z[:, None]
-    return q, r, m + np.log(Z)
+    # the kernels' masked mix (k_edge's rule): only categories with F_c > 0 set m and take a
+    # weight.  Under a Gamma model every F_c > 0 and this is the plain maximum
+    live = F > 0
+    m = np.where(live, sigma, -np.inf).max(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        we = np.where(live, e["weights"][None, :] * np.exp(sigma - m[:, None]), 0.0)
+        Z = (we * F).sum(axis=1)
+        q = (we[:, :, None] * g).sum(axis=1) / Z[:, None]
+        r = we * F / Z[:, None]
+        return q, r, m + np.log(Z)
 
 
 def sweep(orc, tips, tr, e, site_weights=None):

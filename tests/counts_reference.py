@@ -25,11 +25,18 @@ def counts_of(orc, P, S, n, o, t, e, sw):
     X = e["freqs"][None, :, None] * pm  # [c][j][i] = pi_j P_c[j][i]
     F = np.einsum("sci,scj,cji->sc", P[n], P[o], X)
     sigma = S[n] + S[o]
-    m = sigma.max(axis=1)
-    we = e["weights"][None, :] * np.exp(sigma - m[:, None])
-    Z = (we * F).sum(axis=1)
-    coef = sw[:, None] * we / Z[:, None]
-    return np.einsum("sc,sci,scj->cij", coef, P[n], P[o]), float(np.dot(sw, m + np.log(Z)))
+    # the kernels' masked mix (k_edge's rule): only categories with F_c > 0 set m and take a
+    # weight; a pattern of weight 0 adds nothing.  Under a Gamma model every F_c > 0 and this is
+    # the plain maximum
+    live = F > 0
+    m = np.where(live, sigma, -np.inf).max(axis=1)
+    use = sw != 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        we = np.where(live, e["weights"][None, :] * np.exp(sigma - m[:, None]), 0.0)
+        Z = (we * F).sum(axis=1)
+        coef = np.where(use[:, None], sw[:, None] * we / Z[:, None], 0.0)
+        lnl = float(np.dot(sw[use], (m + np.log(Z))[use]))
+    return np.einsum("sc,sci,scj->cij", coef, P[n], P[o]), lnl
 
 
 def sweep(orc, tips, tr, e, site_weights=None):
@@ -82,13 +89,21 @@ def invariant(ref_or_dev, e, orc):
 # ---------------------------------------------------------------- parameters and their shifts
 def shifted(prob, tr, name, delta):
     """(model, rate model, traversal) with parameter `name` moved by `delta`.  Names: "alpha";
+    "pinvar" (the +I models);
     ("rates", k) the k-th GTR exchangeability, GT held at its value; ("freqs", k) pi_k, the last
     frequency taking up the difference; "kappa" (HKY85); ("length", (a, b))."""
     from phylo_utils_amd import substitution_models as SM
-    from phylo_utils_amd.rate_models import GammaRateModel
+    from phylo_utils_amd.rate_models import (GammaRateModel, InvariantGammaModel,
+                                             InvariantSitesModel)
     m, rm, tr2 = prob["model"], prob["rm"], tr
-    if name == "alpha":
+    if name == "alpha" and isinstance(rm, InvariantGammaModel):
+        rm = InvariantGammaModel(rm.pinvar, rm.ncat - 1, rm.alpha + delta)
+    elif name == "alpha":
         rm = GammaRateModel(rm.ncat, rm.alpha + delta)
+    elif name == "pinvar" and isinstance(rm, InvariantGammaModel):
+        rm = InvariantGammaModel(rm.pinvar + delta, rm.ncat - 1, rm.alpha)
+    elif name == "pinvar":
+        rm = InvariantSitesModel(rm.pinvar + delta)
     elif name == "kappa":
         m = SM.HKY85(m._alpha_y + delta, m.freqs)
     elif name[0] == "rates":

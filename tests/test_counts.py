@@ -12,7 +12,8 @@ import counts_reference as R
 from phylo_utils_amd import gradient as G
 from phylo_utils_amd import modelfit, phy
 from phylo_utils_amd import substitution_models as SM
-from phylo_utils_amd.rate_models import GammaRateModel, UniformRateModel
+from phylo_utils_amd.rate_models import (GammaRateModel, InvariantGammaModel,
+                                         InvariantSitesModel, UniformRateModel)
 from phylo_utils_amd.synthetic import CFG2_FREQS, CFG2_GTR_RATES
 
 CPU_CASES = ("dna-pendant-root-4x70-C4", "dna-8x65-C3")
@@ -147,3 +148,91 @@ def test_parameter_names():
     assert np.allclose(m.rates[SM._UPPER], [1, 2, 3, 4, 5, 1])
     f84 = SM.F84(1.5, CFG2_FREQS)
     assert abs(G.kappa_of(f84) - 1.5) < 1e-14
+
+
+# ---------------------------------------------------------------- +I: pinvar
+def _invariant_ref(oracle_mod, case):
+    import invariant_reference as IR
+    prob = IR.problem(case)
+    tr, e, tips, res = R.restate(oracle_mod, prob)
+    return dict(case=case, prob=prob, tr=tr, e=e, tips=tips, res=res)
+
+
+@pytest.mark.parametrize("rm", [InvariantSitesModel(0.3), InvariantGammaModel(0.2, 3, 0.5),
+                                InvariantGammaModel(0.45, 4, 1.7)], ids=repr)
+def test_rate_model_derivs_of_the_invariant_models(rm):
+    """rate_model_derivs against the central difference of rm.rates / rm.weights at h = 1e-6
+    (truncation h^2 f''' / 6 ~ 1e-12, rounding eps / h ~ 2e-10 of the value): 1e-8 of the largest
+    entry."""
+    h = 1e-6
+    names = ["pinvar"] + (["alpha"] if isinstance(rm, InvariantGammaModel) else [])
+    for name in names:
+        def at(delta):
+            prob = dict(model=None, rm=rm)
+            return R.shifted(prob, None, name, delta)[1]
+        hi, lo = at(h), at(-h)
+        dr, dw = G.rate_model_derivs(rm, name)
+        fr, fw = (hi.rates - lo.rates) / (2 * h), (hi.weights - lo.weights) / (2 * h)
+        assert np.abs(dr - fr).max() <= 1e-8 * max(np.abs(fr).max(), 1.0), name
+        assert np.abs(dw - fw).max() <= 1e-8 * max(np.abs(fw).max(), 1.0), name
+        assert dr[0] == 0.0 and abs(dw.sum()) <= 1e-15
+    with pytest.raises(ValueError, match="no parameter"):
+        G.rate_model_derivs(GammaRateModel(4, 0.5), "pinvar")
+
+
+@pytest.mark.parametrize("case", ["dna-8x65-I", "dna-8x65-IG3"])
+def test_model_gradient_pinvar_against_finite_differences(oracle_mod, case):
+    """gradient.model_gradient's "pinvar" (and "alpha" under +I+G) on the restatement's M against
+    central differences of the oracle's lnL: the step (h = 1e-6) and the bound (3.96e-7 of the
+    largest derivative) of test_restatement_against_finite_differences.  Measured worst:
+    dna-8x65-I 8.5e-9 (pinvar), dna-8x65-IG3 4.5e-9."""
+    ref = _invariant_ref(oracle_mod, case)
+    tm = types.SimpleNamespace(substitution_model=ref["prob"]["model"],
+                               rate_model=ref["prob"]["rm"])
+    names = ["pinvar"] + (["alpha"] if case.endswith("IG3") else [])
+    got = G.model_gradient(tm, names, ref["res"])
+    g = np.array([got[n] for n in names])
+    fd = np.array([R.fd_gradient(oracle_mod, ref["prob"], ref["tips"], ref["tr"], n)
+                   for n in names])
+    rg = np.array([R.gradient(oracle_mod, ref["prob"], ref["tr"], ref["res"], n) for n in names])
+    err = np.abs(g - fd) / np.abs(fd).max()
+    print("%s: %s model_gradient %s, finite differences %s, worst %.2e" % (case, names, g, fd,
+                                                                          err.max()))
+    assert err.max() <= 3.96e-7
+    assert np.abs(g - rg).max() <= 1e-8 * np.abs(rg).max()  # test_gradient_module_..'s bound
+    # the invariable category carries a real share of dlnL/dw
+    d_rate, d_weight = G.rate_gradient(tm, ref["res"])
+    assert d_weight[0] > 0 and np.isfinite(d_rate).all()
+    assert np.allclose(d_weight.dot(tm.rate_model.weights), ref["prob"]["weights"].sum(),
+                       rtol=1e-12)
+
+
+def test_pinvar_coordinates_and_parameter_names():
+    """modelfit's logit coordinate: the round trip at pinvar 1e-6, 0.5 and 1 - 1e-6 loses at most
+    the rounding of 1 - p (eps / 2 absolute) through the quotient, the logarithm and back, each
+    of relative error eps on a quantity whose derivative in p is at most 1: 8 eps absolute; the
+    chain rule is dp/dz = p (1 - p)."""
+    eps = np.finfo(float).eps
+    for p in (1e-6, 0.5, 1.0 - 1e-6):
+        co = modelfit._Coordinates({"pinvar": p}, [], [])
+        assert modelfit._LOGIT_BOX[0] < co.x0[0] < modelfit._LOGIT_BOX[1]
+        back = co.values(co.x0)["pinvar"]
+        assert abs(back - p) <= 8 * eps * max(p, 1 - p) and 0 < back < 1
+        g = co.chain(co.x0, {"pinvar": back}, {"pinvar": 3.0}, None)
+        assert abs(g[0] - 3.0 * p * (1 - p)) <= 1e-14
+    gtr, lg = SM.GTR(CFG2_GTR_RATES, CFG2_FREQS), SM.LG()
+    ig, i = InvariantGammaModel(0.2, 3, 0.5), InvariantSitesModel(0.3)
+    assert modelfit.free_parameters(gtr, ig) == ["rates", "freqs", "alpha", "pinvar"]
+    assert modelfit.free_parameters(lg, ig) == ["freqs", "alpha", "pinvar"]
+    assert modelfit.free_parameters(gtr, i) == ["rates", "freqs", "pinvar"]
+    assert modelfit.free_parameters(SM.JC69(), i) == ["pinvar"]
+    with pytest.raises(ValueError, match="valid: rates, freqs, pinvar$"):
+        G.check_params(gtr, i, ["alpha"])
+    m, rm = modelfit.build_models(gtr, ig, dict(pinvar=0.35))
+    assert isinstance(rm, InvariantGammaModel) and rm.pinvar == 0.35 and rm.alpha == 0.5
+    assert rm.ncat == 4 and m is gtr
+    m, rm = modelfit.build_models(gtr, ig, dict(alpha=0.9, pinvar=0.1))
+    assert rm.pinvar == 0.1 and rm.alpha == 0.9
+    m, rm = modelfit.build_models(gtr, i, dict(pinvar=0.6))
+    assert isinstance(rm, InvariantSitesModel) and rm.pinvar == 0.6
+    assert modelfit._values(gtr, ig, ["pinvar", "alpha"]) == {"pinvar": 0.2, "alpha": 0.5}
