@@ -799,6 +799,61 @@ int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes
 int pu_boot_profile(int device, int on);
 int pu_boot_kernel_ms(int device, double *counts_ms, double *newton_ms);
 
+/* ---- Fitch parsimony (normative) ---------------------------------------------
+ * The reference has no parsimony, so there is no reference interface to cite: the rule is
+ * DESIGN 4.22's and tests/parsimony_reference.py restates it.  Every result is an integer and
+ * does not depend on the launch shape, the summation order or the chunking.
+ * The alignment: codes [n_taxa][n_pat] into code_table [n_codes][n_states]; the state set of a
+ * code is bit k for every k with code_table[code][k] > 0.  weights [n_pat] are non-negative
+ * integers, NULL: all 1.  Node ids: a tip is its alignment row (< n_taxa), the internal nodes
+ * are n_taxa .. 2 n_taxa - 3.  A tree is a post-order op list ops [n_taxa - 2][3] = (parent,
+ * left, right) and its root edge [2], the two nodes left without a parent; its 2 n_taxa - 3
+ * edges in op order are 2 i = (left_i, parent_i), 2 i + 1 = (right_i, parent_i) and, last, the
+ * root edge.
+ * PU_E_ARG, before any device is touched: a null buffer other than weights and the optional
+ * outputs, n_taxa < 3 or > PU_PARS_MAX_TAXA (a workgroup keeps one 64-bit counter per edge in
+ * LDS), n_pat < 1, n_states outside [1, 32], n_codes outside [1, 32], a code >= n_codes, a
+ * code that allows no state, a negative weight or weights that sum past 2^63 / (2 n_taxa), an
+ * op list that is not a post-order of a binary tree over exactly the alignment's rows, an
+ * order that is not a permutation, n_trees, n_query or n_rep < 1.
+ * The node sets of one launch live in a device workspace of at most 256 MiB, laid out
+ * [node][pattern]; a call is cut into chunks of trees (or replicates) and, where one tree
+ * alone is larger, of patterns.  PU_PARS_CHUNK=n, read at each call, caps the trees or
+ * replicates of a chunk. */
+#define PU_PARS_MAX_TAXA 4000
+/* The lengths of n_trees trees (ops [n_trees][n_taxa-2][3], root_edges [n_trees][2]) in one
+ * launch per chunk: lengths_out [n_trees]; pattern_changes_out [n_trees][n_pat], nullable,
+ * the unweighted changes of every pattern; edge_changes_out [n_trees][2 n_taxa - 3], nullable,
+ * per edge in op order the weighted count of patterns whose two directional sets are disjoint. */
+int pu_fitch_lengths(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                     const uint8_t *codes, const double *code_table, const int64_t *weights,
+                     int n_trees, const int32_t *ops, const int32_t *root_edges,
+                     uint64_t *lengths_out, uint32_t *pattern_changes_out,
+                     uint64_t *edge_changes_out);
+/* The exact length of the tree with query row q (query_codes [n_query][n_pat]) attached on
+ * edge e, for every q and e: lengths_out [n_query][2 n_taxa - 3], edges in op order.  The edge
+ * sets are computed once ([edge][pattern], not chunked); the scoring is a grid over pattern
+ * tiles, edges and query tiles. */
+int pu_fitch_insert_lengths(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                            const uint8_t *codes, const double *code_table,
+                            const int64_t *weights, const int32_t *ops, const int32_t *root_edge,
+                            int n_query, const uint8_t *query_codes, uint64_t *lengths_out);
+/* Stepwise addition for n_rep addition orders [n_rep][n_taxa], each a permutation of the rows:
+ * edges_out [n_rep][2 n_taxa - 3][2] in DESIGN 4.22's numbering, step_lengths_out
+ * [n_rep][n_taxa - 2] (entry 0: the three-taxon star) and lengths_out [n_rep], the length of
+ * the finished tree scored once more from scratch.  The host drives the steps (one read-back
+ * per step: the per-edge sums, then the argmin and the topology update); all replicates of a
+ * chunk go through the same launch of a step. */
+int pu_parsimony_stepwise(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                          const uint8_t *codes, const double *code_table, const int64_t *weights,
+                          int n_rep, const int32_t *orders, int32_t *edges_out,
+                          uint64_t *step_lengths_out, uint64_t *lengths_out);
+/* Event timing (scripts/time_parsimony.py): with pu_parsimony_profile(device, 1) every call
+ * above records events around its launches; pu_parsimony_kernel_ms returns the last call's
+ * kernel time in ms, summed over its chunks and steps. */
+int pu_parsimony_profile(int device, int on);
+int pu_parsimony_kernel_ms(int device, double *ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -32,6 +32,13 @@ no tree builder), written as Newick to ``-o`` when given, and the ``lnL = `` lin
 after ``--optimise`` when asked; with ``--bootstrap R`` (and the seed of ``--seed``) the Newick
 carries, as internal node labels, the support in percent of every split over R bootstrap
 replicates (``phylo_utils_amd.bootstrap``);
+``-s aln.fasta -m MODEL --parsimony [R] [-o tree.nwk]`` needs no ``-t`` either and excludes
+``--nj``: the tree is the shortest of R (default 1) randomised stepwise-addition trees under Fitch
+parsimony (``phylo_utils_amd.parsimony``, the seed of ``--seed``; the reference has no tree
+builder), written to ``-o`` when given; one extra line ``parsimony = <length>`` comes before the
+``lnL = `` line, and ``--nni``, ``--spr``, ``--optimise``, ``--support`` and ``-o`` follow as they do
+after ``--nj``.  ``--parsimony-score`` (after ``-t`` or ``--nj``) prints the same line for that tree
+and changes nothing else;
 ``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
 interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
 rounds, default 50); ``-o`` then receives the final Newick;
@@ -185,6 +192,13 @@ def parse_cli(argv=None):
     ap.add_argument("--nj", choices=["nj", "bionj"], default=None,
                     help="take the tree from neighbour joining (or BIONJ) on the pairwise ML "
                          "distances of -s (no -t); -o receives its Newick")
+    ap.add_argument("--parsimony", type=int, nargs="?", const=1, default=None, metavar="R",
+                    help="take the tree from randomised stepwise addition under Fitch parsimony, "
+                         "the shortest of R addition orders (default 1; seed: --seed; no -t, no "
+                         "--nj); prints a 'parsimony = ' line; -o receives its Newick")
+    ap.add_argument("--parsimony-score", action="store_true", dest="parsimony_score",
+                    help="after -t or --nj: print the tree's Fitch parsimony length as a "
+                         "'parsimony = ' line before the lnL line")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="R",
                     help="with --nj: label the tree's splits with their support in percent "
                          "over R bootstrap replicates (seed: --seed)")
@@ -277,6 +291,21 @@ def validate_args(args):
             raise ValueError("--bootstrap needs --nj")
         if args.bootstrap < 1:
             raise ValueError("--bootstrap needs at least one replicate")
+    if getattr(args, "parsimony", None) is not None:
+        if args.tree is not None or getattr(args, "nj", None) is not None:
+            raise ValueError("--parsimony excludes -t and --nj")
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--parsimony excludes --distances and --simulate")
+        if args.parsimony < 1:
+            raise ValueError("--parsimony needs at least one addition order")
+        if args.alignment is None:
+            raise ValueError("Alignment file not specified")
+        if not os.path.exists(args.alignment):
+            raise FileNotFoundError("Alignment file {} does not exist".format(args.alignment))
+        return
+    if getattr(args, "parsimony_score", False):
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--parsimony-score excludes --distances and --simulate")
     if getattr(args, "nj", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None \
                 or args.tree is not None:
@@ -313,14 +342,16 @@ def validate_args(args):
 def run(args, out=None):
     out = sys.stdout if out is None else out
     nj = getattr(args, "nj", None)
-    if nj is None:
+    pars = getattr(args, "parsimony", None)
+    pars_length = None
+    if nj is None and pars is None:
         with open(args.tree) as fh:
             tree = parse_newick(fh.read())
     aln = A.read_fasta(args.alignment)
     desc = parse_model_string(args.model)
     alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
     tm = TreeModel(device=args.device)
-    if nj is None:
+    if nj is None and pars is None:
         tm.set_tree(tree)
     tm.set_alignment(aln, alphabet)
     tm.set_rate_model(build_rate_model(desc))
@@ -333,6 +364,13 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
+    if pars is not None:  # --parsimony: the shortest of R stepwise-addition trees
+        tree, pars_length, _ = tm.set_parsimony_tree(n_rep=pars, seed=args.seed)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
+    elif getattr(args, "parsimony_score", False):
+        pars_length = tm.parsimony_length()
     if args.ascertainment:
         tm.set_ascertainment_bias_correction(weighted=args.ascertainment == "weighted")
     tm.initialise()
@@ -402,6 +440,8 @@ def run(args, out=None):
             for i, (r, k) in enumerate(zip(rate, cat.argmax(axis=1))):
                 fh.write("{}\t{:.10g}\t{}\n".format(i + 1, r, int(k) + 1))
     lnl = tm.compute_likelihood_at_edge(*tm.traversal.root_edge).sum()
+    if pars_length is not None:
+        out.write("parsimony = {}\n".format(pars_length))
     if fitted is not None:
         out.write("model = {}\n".format(fitted))
     out.write("lnL = {}\n".format(lnl))

@@ -750,6 +750,41 @@ class TreeModel(object):
         self.set_tree(tree)
         return tree
 
+    def parsimony_length(self, per_pattern=False):
+        """The Fitch parsimony length of the model's tree on its own alignment and
+        ``siteweights`` (``parsimony.fitch_lengths``), an integer; with
+        `per_pattern` also the unweighted changes of every pattern, in pattern order as
+        ``sitewise_patterns`` gives them.  Needs no context and no model, and leaves the
+        likelihood state as it is."""
+        from . import parsimony
+        if getattr(self, "tree", None) is None:
+            raise ValueError("No tree has been set")
+        codes, table, names = self._coded_alignment()
+        return parsimony.fitch_lengths((codes, table, names), self.tree,
+                                       weights=self.siteweights, per_pattern=per_pattern,
+                                       device=self.device)
+
+    def set_parsimony_tree(self, n_rep=1, seed=0, min_length=1e-8):
+        """A starting tree by randomised stepwise addition under Fitch parsimony
+        (``parsimony.stepwise_addition``): `n_rep` random addition orders
+        (``parsimony.random_orders(n, n_rep, seed)``), the shortest tree kept, ties to the lowest
+        replicate.  Every branch length is ``max(edge change count / sum of siteweights,
+        min_length)``.  Needs coded tips and no model at all, so it also serves the
+        non-reversible models ``set_nj_tree`` refuses.  Calls ``set_tree``; returns (tree,
+        length, the lengths of all replicates)."""
+        from . import parsimony
+        aln = self._coded_alignment()
+        w = parsimony.integer_weights(self.siteweights, aln[0].shape[1])
+        edges, _, lengths = parsimony.stepwise_addition(aln, n_rep=n_rep, seed=seed, weights=w,
+                                                        device=self.device)
+        best = int(np.argmin(lengths))  # the first of equal lengths
+        tree = parsimony.edges_to_tree(edges[best], aln[2])
+        _, per_edge = parsimony.fitch_lengths(aln, tree, weights=w, per_edge=True,
+                                              device=self.device)
+        tree = parsimony.edge_lengths_tree(tree, aln[2], per_edge, int(w.sum()), min_length)
+        self.set_tree(tree)
+        return tree, int(lengths[best]), lengths
+
     def bootstrap_nj(self, n_replicates=100, seed=0, method="nj", **distance_kw):
         """``set_nj_tree`` with bootstrap support (``bootstrap.bootstrap_nj`` on the model's own
         alignment and models): the reference tree becomes the model's tree, as ``set_nj_tree``
