@@ -18,16 +18,12 @@
 
 #include "pu_ctx.h"
 #include "pu_minimise.h"
+#include "pu_newton.h"
 #include "pu_resident.h"
 
 using namespace pu;
 
 namespace {
-
-// MIN_BRANCH_LENGTH of the reference is 2^-16 (substitution_models/abstract.py:8, unused
-// there); the optimiser bounds lengths to [kMinLen, kMaxLen]
-constexpr double kMinLen = 1e-8;
-constexpr double kMaxLen = 100.0;
 
 int node_src(pu_ctx *c, int node, NodeSrc *out) {
     if (node < 0 || node >= c->n_nodes)
@@ -506,61 +502,31 @@ int device_newton(pu_ctx *c, const NodeSrc &sa, const NodeSrc &sb, double t0, do
     return PU_OK;
 }
 
-// Newton-Raphson on one edge length with a monotone safeguard: a step that lowers the lnL
-// is halved (up to 30 times); a non-concave point moves by expansion (d1 > 0) or halving.
+// The Newton rule of pu_newton.h on one edge length (the reference's MIN_BRANCH_LENGTH is 2^-16,
+// substitution_models/abstract.py:8, unused there; the rule's bounds are kMinLen, kMaxLen): the
+// whole loop in one launch where device_newton takes it, else one k_edge launch per evaluation.
 int newton(pu_ctx *c, int na, int nb, int key, double tol, int max_iter, double *len_io,
            double *lnl_out, int *iters_out) {
     NodeSrc sa, sb;
     int rc;
     if ((rc = node_src(c, na, &sa)) || (rc = node_src(c, nb, &sb))) return rc;
-    double t = std::min(std::max(*len_io, kMinLen), kMaxLen);
-    {
-        double td, rd[3];
-        int itd;
-        rc = device_newton(c, sa, sb, t, tol, max_iter, &td, rd, &itd);
-        if (rc < 0) return rc;
-        if (rc == 0) {
-            *len_io = td;
-            set_len(c, key, td);
-            if (lnl_out) *lnl_out = rd[0];
-            if (iters_out) *iters_out = itd;
-            return PU_OK;
-        }
-    }
+    NewtonState s;
+    newton_start(s, *len_io);
     double r[3];
-    if ((rc = derivs_at(c, sa, sb, t, r))) return rc;
-    int it = 0;
-    for (; it < max_iter; ++it) {
-        const double l = r[0], d1 = r[1], d2 = r[2];
-        if (!std::isfinite(l)) break;
-        double step = d2 < 0.0 ? -d1 / d2 : (d1 > 0.0 ? t + 0.1 : -0.5 * t);
-        double tn = std::min(std::max(t + step, kMinLen), kMaxLen);
-        if (tn == t) break;
-        double rn[3];
-        bool ok = false;
-        for (int h = 0; h < 30; ++h) {
-            if ((rc = derivs_at(c, sa, sb, tn, rn))) return rc;
-            if (rn[0] >= l - 1e-13 * fabs(l)) {
-                ok = true;
-                break;
-            }
-            tn = 0.5 * (t + tn);
-        }
-        if (!ok) break;  // no ascent along this direction: t is (numerically) optimal
-        const double dt = fabs(tn - t);
-        t = tn;
-        r[0] = rn[0];
-        r[1] = rn[1];
-        r[2] = rn[2];
-        if (dt <= tol * (1.0 + t)) {
-            ++it;
-            break;
+    rc = device_newton(c, sa, sb, s.tn, tol, max_iter, &s.t, r, &s.it);
+    if (rc < 0) return rc;
+    if (rc == 0) {
+        s.lnl = r[0];
+    } else {
+        while (!s.done) {
+            if ((rc = derivs_at(c, sa, sb, s.tn, r))) return rc;
+            newton_step(s, r[0], r[1], r[2], tol, max_iter);
         }
     }
-    *len_io = t;
-    set_len(c, key, t);
-    if (lnl_out) *lnl_out = r[0];
-    if (iters_out) *iters_out = it;
+    *len_io = s.t;
+    set_len(c, key, s.t);
+    if (lnl_out) *lnl_out = s.lnl;
+    if (iters_out) *iters_out = s.it;
     return PU_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "pu_internal.h"
 #include "pu_edge_dev.h"
 #include "pu_minimise.h"
+#include "pu_newton.h"
 #include "pu_resident.h"
 
 #include <math.h>
@@ -547,9 +548,9 @@ __global__ void __launch_bounds__(256) k_ascbias(AscArgs a) {
 }
 
 // ---- device-side Newton on one edge (NewtonArgs, pu_internal.h; r06) ----
-// pu_edge.cpp's newton() -- the same steps, safeguards and stopping rule -- in one persistent
-// launch.  An evaluation needs, per (site, category), f = sum_i pi_i (P(0) a)_i (P(t) b)_i and
-// its two t-derivatives.  With P(t) = V diag(e^{l r t}) V^-1 (the eigen form k_pmatrix and
+// The Newton rule of pu_newton.h -- the host loop's steps, safeguards and stopping rule -- in
+// one persistent launch.  An evaluation needs, per (site, category),
+// f = sum_i pi_i (P(0) a)_i (P(t) b)_i and its two t-derivatives.  With P(t) = V diag(e^{l r t}) V^-1 (the eigen form k_pmatrix and
 // build_p use) that is f = sum_k c_k e^{l_k r t}, f' = sum_k c_k (l_k r) e^{..}, f'' = sum_k
 // c_k (l_k r)^2 e^{..}, c_k = [V^T (pi o P(0) a)]_k [V^-1 b]_k: K coefficients per (site,
 // category), computed once per launch and held in registers, so an evaluation reads no CLV
@@ -557,7 +558,6 @@ __global__ void __launch_bounds__(256) k_ascbias(AscArgs a) {
 // differs from k_edge's direct products by ~1e-16 relative per site (tests: 1e-12 on lnL and
 // derivatives, the same optimum to 1e-9).  A wave owns `tpw` whole tiles, all categories;
 // the categories of a site are mixed in registers exactly as k_edge does.
-constexpr double kNewtonMinLen = 1e-8, kNewtonMaxLen = 100.0;  // pu_edge.cpp kMinLen / kMaxLen
 constexpr int kNewtonMaxC = 4;   // categories held per lane
 constexpr int kNewtonTpw = 2;    // tiles per wave held in registers at most (template TPW)
 constexpr int kNewtonWaves = 4;  // 256-thread workgroups
@@ -602,7 +602,7 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
     __shared__ double vsum[3 * 256];                           // the combiner's slot sums
     __shared__ double wred[3 * kNewtonWaves];                  // the waves' sums
     __shared__ double sh_next[2];
-    __shared__ double sh_nt[7];  // the combiner's newton() state: t, lnL, d1, d2, next t, iterations, halvings
+    __shared__ NewtonState sh_nt;  // the combiner's state of the Newton rule (pu_newton.h)
     __shared__ MinState sh_ms;   // ... or brent's / dbrent's (NewtonArgs::mode)
     __shared__ double sh_mpar[4];  // their lo, t0, hi, tol
     __shared__ double sh_ss[TPW * kNewtonMaxC * 256];         // log scalers per tile, category, lane
@@ -840,13 +840,12 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
                 const double r0 = wave_total(((vsum[l] + vsum[64 + l]) + vsum[128 + l]) + vsum[192 + l]);
                 const double r1 = wave_total(((vsum[256 + l] + vsum[320 + l]) + vsum[384 + l]) + vsum[448 + l]);
                 const double r2 = wave_total(((vsum[512 + l] + vsum[576 + l]) + vsum[640 + l]) + vsum[704 + l]);
-                // newton()'s loop, one evaluation at a time; every lane of the wave holds the same
-                // sums (read from lane 63) and so the same state
-                // the state lives in LDS between evaluations (registers across the loop spill)
-                double nt_t = sh_nt[0], nt_l = sh_nt[1], nt_d1 = sh_nt[2], nt_d2 = sh_nt[3];
-                double nt_tn = sh_nt[4];
-                int nt_it = (int)sh_nt[5], nt_h = (int)sh_nt[6];
-                bool done = abort, plan = false;
+                // the rule of pu_newton.h, one evaluation at a time; every lane of the wave holds
+                // the same sums (read from lane 63) and so steps the same state, which lives in
+                // LDS between evaluations (registers across the loop spill)
+                NewtonState nt = sh_nt;
+                double next = 0.0;
+                bool done = abort;
                 if (n.mode != PU_MIN_NEWTON) {
                     // brent / dbrent (pu_minimise.h, src/optimisation.pyx) on f = -lnL and
                     // f' = -dlnL/dt: one lane steps the state machine, whose state stays in LDS
@@ -859,42 +858,12 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
                         nx = min_step(sh_ms, -r0, -r1);
                         dn = sh_ms.done;
                     }
-                    nt_tn = __shfl(nx, 0);
+                    next = __shfl(nx, 0);
                     done = abort || __shfl(dn, 0) != 0;
-                } else if (abort) {
-                } else if (evn == 0) {
-                    nt_t = nt_tn = x;
-                    nt_l = r0;
-                    nt_d1 = r1;
-                    nt_d2 = r2;
-                    nt_it = nt_h = 0;
-                    plan = true;
-                } else if (r0 >= nt_l - 1e-13 * fabs(nt_l)) {  // accepted
-                    const double dt = fabs(nt_tn - nt_t);
-                    nt_t = nt_tn;
-                    nt_l = r0;
-                    nt_d1 = r1;
-                    nt_d2 = r2;
-                    ++nt_it;
-                    if (dt <= n.tol * (1.0 + nt_t))
-                        done = true;
-                    else
-                        plan = true;
-                } else if (++nt_h >= 30) {
-                    done = true;  // no ascent along this direction
-                } else {
-                    nt_tn = 0.5 * (nt_t + nt_tn);
-                }
-                if (plan) {
-                    if (nt_it >= n.max_iter || !isfinite(nt_l)) {
-                        done = true;
-                    } else {
-                        const double step = nt_d2 < 0.0 ? -nt_d1 / nt_d2
-                                                         : (nt_d1 > 0.0 ? nt_t + 0.1 : -0.5 * nt_t);
-                        nt_tn = fmin(fmax(nt_t + step, kNewtonMinLen), kNewtonMaxLen);
-                        nt_h = 0;
-                        if (nt_tn == nt_t) done = true;
-                    }
+                } else if (!abort) {
+                    if (evn == 0) newton_start(nt, x);
+                    next = newton_step(nt, r0, r1, r2, n.tol, n.max_iter);
+                    done = nt.done != 0;
                 }
                 if (done && l == 0) {  // the host's result, in mapped memory, then its sequence number
                     if (n.mode != PU_MIN_NEWTON) {  // out = (x, f(x), iterations); lnL = -f
@@ -904,11 +873,11 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
                         n.res[3] = 0.0;
                         n.res[4] = (double)sh_ms.res_it;
                     } else {
-                        n.res[0] = nt_t;
-                        n.res[1] = nt_l;
-                        n.res[2] = nt_d1;
-                        n.res[3] = nt_d2;
-                        n.res[4] = (double)nt_it;
+                        n.res[0] = nt.t;
+                        n.res[1] = nt.lnl;
+                        n.res[2] = nt.d1;
+                        n.res[3] = nt.d2;
+                        n.res[4] = (double)nt.it;
                     }
                     n.res[5] = (double)(evn + 1);
                     n.res[6] = abort ? 1.0 : 0.0;
@@ -918,7 +887,7 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
                 // 8 publication lines of 64 bytes, one per group of pollers: the next length's two
                 // halves, each beside flag = 2 generation + done (all ones: abort); lanes 0-15
                 if (l < 16) {
-                    const uint64_t bits = (uint64_t)__double_as_longlong(nt_tn);
+                    const uint64_t bits = (uint64_t)__double_as_longlong(next);
                     const uint64_t half = (l & 1) ? bits >> 32 : bits & 0xffffffffull;
                     const unsigned flag = abort ? 0xffffffffu : 2u * ge + (done ? 1u : 0u);
                     int off = 8 * (l >> 1) + (l & 1);
@@ -928,14 +897,8 @@ __global__ void __launch_bounds__(64 * kNewtonWaves, TPW == 1 ? 3 : 2)
                 }
                 if (l == 0) {
                     stamp(evn, 3);
-                    sh_nt[0] = nt_t;
-                    sh_nt[1] = nt_l;
-                    sh_nt[2] = nt_d1;
-                    sh_nt[3] = nt_d2;
-                    sh_nt[4] = nt_tn;
-                    sh_nt[5] = nt_it;
-                    sh_nt[6] = nt_h;
-                    sh_next[0] = nt_tn;
+                    sh_nt = nt;
+                    sh_next[0] = next;
                     sh_next[1] = done ? 1.0 : 0.0;
                 }
             }

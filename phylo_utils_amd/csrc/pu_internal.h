@@ -235,21 +235,21 @@ struct AscArgs {
 };
 int launch_ascbias(hipStream_t st, const AscArgs &a);
 // Device-side Newton-Raphson on one edge length (r06): one persistent launch
-// runs the whole loop of pu_edge.cpp's newton() -- its safeguards, bounds and stopping rule --
+// runs the whole Newton rule of pu_newton.h -- its safeguards, bounds and stopping rule --
 // with every evaluation a grid-wide reduction, so the host pays one launch and one poll per
 // optimisation instead of one per evaluation.  Each wave holds `tpw` tiles' eigen-space
 // coefficients in registers (pu_edge.hip k_edge_newton).  After an evaluation every workgroup
 // stores its sums into its own 64-byte slot as six 8-byte words, each a 32-bit half beside the
 // evaluation's 32-bit generation (single-copy atomic: no drain, one read); workgroup 0, the
-// combiner, polls every slot in parallel, adds them in a fixed order, takes newton()'s next
-// step (state in its registers) and publishes the next length the same way on 8 lines, one per
+// combiner, polls every slot in parallel, adds them in a fixed order, takes the rule's next
+// step (newton_step; state in its LDS) and publishes the next length the same way on 8 lines, one per
 // group of pollers (bounded spins: a timeout ends every workgroup and reports an error).
 // Generations are monotone across launches (base), so nothing is reset between launches.
 // Grid: sized to be co-resident (occupancy API with a margin).
 constexpr int kNewtonState = 8;    // NewtonArgs::res doubles
 constexpr unsigned kNewtonSpins = 1u << 20;  // bounded polls (a load + s_sleep each): ~1 s
 struct NewtonArgs {
-    double t0, tol, seq;           // start length, newton()'s tol; seq: res[7] when done
+    double t0, tol, seq;           // start length, newton_step's tol; seq: res[7] when done
     int max_iter, tpw;             // tpw: tiles per wave
     int plain;                     // 1: an ordinary launch of the co-resident grid (not cooperative)
     int mode;                      // PU_MIN_NEWTON, PU_MIN_BRENT, PU_MIN_DBRENT (pu_minimise.h)

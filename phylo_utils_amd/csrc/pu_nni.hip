@@ -33,16 +33,13 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_newton.h"
 #include "pu_resident.h"
 #include "pu_service.h"
 
 using namespace pu;
 
 namespace {
-
-// MIN / MAX length of the optimisers (pu_edge.cpp kMinLen / kMaxLen)
-constexpr double kMinLen = 1e-8;
-constexpr double kMaxLen = 100.0;
 
 struct QuartetArgs {
     NodeSrc x[4];
@@ -319,53 +316,6 @@ int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, 
     return PU_OK;
 }
 
-// pu_edge.cpp's newton() as a state machine, so that three of them advance on one launch per
-// step: the same steps, safeguards (a step that lowers the lnL is halved, up to 30 times; a
-// non-concave point moves by expansion or halving), bounds and stopping rule
-struct Newton {
-    double t, r[3], tn;
-    int it = 0, h = 0, evals = 0;
-    bool started = false, done = false;
-
-    double start(double t0) {
-        t = tn = std::min(std::max(t0, kMinLen), kMaxLen);
-        return tn;
-    }
-    void plan(int max_iter) {
-        if (it >= max_iter || !std::isfinite(r[0])) {
-            done = true;
-            return;
-        }
-        const double step = r[2] < 0.0 ? -r[1] / r[2] : (r[1] > 0.0 ? t + 0.1 : -0.5 * t);
-        tn = std::min(std::max(t + step, kMinLen), kMaxLen);
-        h = 0;
-        if (tn == t) done = true;
-    }
-    // the evaluation at tn has arrived
-    void step(const double *rn, double tol, int max_iter) {
-        ++evals;
-        if (!started) {
-            started = true;
-            for (int k = 0; k < 3; ++k) r[k] = rn[k];
-            plan(max_iter);
-        } else if (rn[0] >= r[0] - 1e-13 * fabs(r[0])) {
-            const double dt = fabs(tn - t);
-            t = tn;
-            for (int k = 0; k < 3; ++k) r[k] = rn[k];
-            ++it;
-            if (dt <= tol * (1.0 + t))
-                done = true;
-            else
-                plan(max_iter);
-        } else if (++h >= 30) {
-            done = true;  // no ascent along this direction: t is (numerically) optimal
-        } else {
-            tn = 0.5 * (t + tn);
-        }
-        if (done) tn = t;
-    }
-};
-
 // ---- branch support -----------------------------------------------------------
 
 // the pattern weights as a weight row of the RELL product (integers, checked on the host)
@@ -628,21 +578,24 @@ int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, doubl
                 return rc;
             l[i] = c->up_len[key];
         }
-        Newton nt[3];
+        // the rule of pu_newton.h, three of them advancing on one launch per step; a finished
+        // one is evaluated along at its optimum (tn == t)
+        NewtonState nt[3];
         double t[3], out9[9];
-        for (int k = 0; k < 3; ++k) t[k] = nt[k].start(c->up_len[kc]);
+        for (int k = 0; k < 3; ++k) t[k] = newton_start(nt[k], c->up_len[kc]);
         while (!(nt[0].done && nt[1].done && nt[2].done)) {
             if ((rc = quartet_eval(c, x, l, t, out9))) return rc;
             for (int k = 0; k < 3; ++k) {
-                if (!nt[k].done) nt[k].step(out9 + 3 * k, tol, max_iter);
+                const double *r = out9 + 3 * k;
+                if (!nt[k].done) newton_step(nt[k], r[0], r[1], r[2], tol, max_iter);
                 t[k] = nt[k].tn;
             }
         }
         for (int k = 0; k < 3; ++k) {
             double *s = scores_out + 12 * (size_t)n_scored + 4 * k;
             s[0] = nt[k].t;
-            s[1] = nt[k].r[0];
-            s[2] = nt[k].r[1];
+            s[1] = nt[k].lnl;
+            s[2] = nt[k].d1;
             s[3] = (double)nt[k].evals;
         }
         int32_t *qo = quartets_out + 6 * (size_t)n_scored;

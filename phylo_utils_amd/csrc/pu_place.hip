@@ -28,7 +28,7 @@
 // the log table G[p][code] = m_p + log sum_c sum_k W_pc(k) e^{lambda_k r_c l0} u_k(code).
 // k_place_prescore adds sw_s G[p(s)][code_qs] over fixed chunks of kPlaceChunk sites, one
 // workgroup per (query, chunk), and k_place_chunk_sum adds a query's chunks in ascending order.
-// k_place_newton runs pu_edge.cpp's newton() for one query per workgroup on W.  Every sum runs
+// k_place_newton runs the Newton rule (pu_newton.h) for one query per workgroup on W.  Every sum runs
 // in a fixed order and nothing written is read by another workgroup of the same launch: two
 // runs are bitwise equal, and a query's numbers do not depend on the other queries.
 #include <math.h>
@@ -38,6 +38,7 @@
 
 #include "pu_ctx.h"
 #include "pu_edge_dev.h"
+#include "pu_newton.h"
 #include "pu_resident.h"
 #include "pu_service.h"
 
@@ -55,8 +56,6 @@ constexpr int kPlaceThreads = 256;  // k_place_prescore, k_place_chunk_sum
 // refine pass of 5000 candidates over 97 edges (cfg2) took 770 ms with 4 waves
 constexpr int kNewtonThreads = 1024;
 constexpr int kPlaceMaxCK = 256;    // C * K of any context the table kernel takes (64 x 4)
-constexpr double kMinLen = 1e-8;    // pu_edge.cpp kMinLen / kMaxLen
-constexpr double kMaxLen = 100.0;
 
 __host__ __device__ inline int place_waves(int C) {
     return C < kPlaceMaxWaves ? C : kPlaceMaxWaves;
@@ -299,7 +298,7 @@ struct NewtonArgsP {
     double *out;  // [n][5]: l*, lnL(l*), dlnL/dl, d2lnL/dl2, steps
 };
 
-// One workgroup per query: pu_edge.cpp's newton() on the pendant length, every evaluation a
+// One workgroup per query: the Newton rule (pu_newton.h) on the pendant length, every evaluation a
 // pass of the workgroup's 1024 threads over the query's sites.  Per evaluation e^{lambda_k r_c l}
 // and its factors (lambda_k r_c), (lambda_k r_c)^2 stand in LDS; a thread adds its sites in
 // ascending order, then a fixed 64-lane tree, then the sixteen waves in order.  Every thread takes
@@ -376,46 +375,21 @@ __global__ void __launch_bounds__(kNewtonThreads) k_place_newton(QueryDev d, New
         }
     };
 
-    // pu_edge.cpp newton(): a step that lowers the lnL is halved (up to 30 times); a non-concave
-    // point moves by expansion (d1 > 0) or halving; lengths stay in [kMinLen, kMaxLen]
-    double t = fmin(fmax(n.l0, kMinLen), kMaxLen);
-    double r[3];
-    eval(t, r);
-    int it = 0;
-    for (; it < n.max_iter; ++it) {
-        const double lnl = r[0], d1 = r[1], d2 = r[2];
-        if (!isfinite(lnl)) break;
-        const double step = d2 < 0.0 ? -d1 / d2 : (d1 > 0.0 ? t + 0.1 : -0.5 * t);
-        double tn = fmin(fmax(t + step, kMinLen), kMaxLen);
-        if (tn == t) break;
-        double rn[3];
-        bool ok = false;
-        for (int h = 0; h < 30; ++h) {
-            eval(tn, rn);
-            if (rn[0] >= lnl - 1e-13 * fabs(lnl)) {
-                ok = true;
-                break;
-            }
-            tn = 0.5 * (t + tn);
-        }
-        if (!ok) break;  // no ascent along this direction: t is (numerically) optimal
-        const double dt = fabs(tn - t);
-        t = tn;
-        r[0] = rn[0];
-        r[1] = rn[1];
-        r[2] = rn[2];
-        if (dt <= n.tol * (1.0 + t)) {
-            ++it;
-            break;
-        }
+    // every thread steps a state of its own from the same sums: no broadcast
+    NewtonState s;
+    newton_start(s, n.l0);
+    while (!s.done) {
+        double r[3];
+        eval(s.tn, r);
+        newton_step(s, r[0], r[1], r[2], n.tol, n.max_iter);
     }
     if (threadIdx.x == 0) {
         double *o = n.out + 5 * (size_t)blockIdx.x;
-        o[0] = t;
-        o[1] = r[0];
-        o[2] = r[1];
-        o[3] = r[2];
-        o[4] = (double)it;
+        o[0] = s.t;
+        o[1] = s.lnl;
+        o[2] = s.d1;
+        o[3] = s.d2;
+        o[4] = (double)s.it;
     }
 }
 

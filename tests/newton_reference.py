@@ -1,5 +1,5 @@
 """The branch-length Newton rule once more, in plain Python floats, with a trace of every branch
-it takes.  The rule is pu_edge.cpp's newton():
+it takes.  The rule is csrc/pu_newton.h's:
 
 * lengths are kept in [1e-8, 100];
 * the step is -d1 / d2 where d2 < 0; where d2 >= 0 it is t + 0.1 for d1 > 0 (`expand`), else

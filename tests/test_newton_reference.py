@@ -2,8 +2,11 @@
 (parallel.newton_edge) and the oracle's (oracle.newton_edge, the one nni_reference uses) on
 closed-form evaluate functions, each built to take one branch of the rule: the expected events in
 order, and (t, lnL, iterations) equal bit for bit.  The functions need not be likelihoods, nor
-even have the derivatives they report: the rule sees three numbers per length."""
+even have the derivatives they report: the rule sees three numbers per length.  The library's
+C++ rule (csrc/pu_newton.h) replays the same runs on the host (tests/newton_check.cpp)."""
 import math
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +15,10 @@ import newton_cases as NC
 import newton_reference as NT
 import place_reference as PR
 
+from conftest import ROOT
 from phylo_utils_amd.parallel import newton_edge
 
+CSRC = os.path.join(ROOT, "phylo_utils_amd", "csrc")
 TOL = 1e-8
 
 # a concave lnL falling from 0: the step from 0.1 passes the lower bound, the bound is accepted
@@ -95,6 +100,39 @@ def test_closed_form_case_takes_its_branch(oracle_mod, case):
         got = copy(counted, t0, TOL, max_iter)
         assert got == (t, lnl, it), (copy.__module__, got, (t, lnl, it))
         assert calls[0] == trace.evaluations
+
+
+def test_cpp_rule_replays_every_closed_form_case(tmp_path):
+    """The C++ rule (csrc/pu_newton.h, the one every driver in the library steps) on the same
+    twelve cases, on the host: tests/newton_check.cpp replays each run of the traced reference
+    and must name every abscissa the reference evaluated, be done exactly when the reference
+    stops, and end on its (t, lnL, d1, d2, iterations, evaluations), all bit for bit."""
+    hx = lambda v: float(v).hex()
+    lines = []
+    for case in sorted(CASES):
+        f, t0, max_iter, _, _ = CASES[case]
+        seen = []
+
+        def recorded(t):
+            seen.append((t,) + tuple(float(v) for v in f(t)))
+            return seen[-1][1:]
+
+        t, lnl, d1, d2, it, trace = NT.newton_trace(recorded, t0, TOL, max_iter)
+        assert len(seen) == trace.evaluations and (case != "flat-gives-up" or len(seen) == 31)
+        lines.append("case %s %s %s %d %d" % (case, hx(t0), hx(TOL), max_iter, len(seen)))
+        lines += [" ".join(hx(v) for v in row) for row in seen]
+        lines.append("end %s %d %d" % (" ".join(hx(v) for v in (t, lnl, d1, d2)), it, len(seen)))
+    script = tmp_path / "newton_cases.txt"
+    script.write_text("\n".join(lines) + "\n")
+    obj = str(tmp_path / "obj")
+    build = subprocess.run(["make", "-C", CSRC, "OBJ=" + obj, "newton_check"],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stdout + build.stderr
+    run = subprocess.run([os.path.join(obj, "newton_check"), str(script)], capture_output=True,
+                         text=True)
+    print(run.stdout)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert len(CASES) == 12 and "12 cases" in run.stdout and " 0 failures" in run.stdout
 
 
 def test_margins_of_a_trace():
