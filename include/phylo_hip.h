@@ -717,6 +717,23 @@ int pu_boot_weights(int device, uint64_t seed, int64_t first_rep, int n_rep, int
 int pu_boot_weights_device(int device, void *stream, uint64_t seed, int64_t first_rep, int n_rep,
                            int64_t n_sites, const double *d_site_weights, uint32_t *d_w,
                            int64_t ldw);
+/* Scaled resampling (normative; the multiscale bootstrap of the AU test): the rule
+ * above with j = 0..n_draw-1 -- c = min(floor(u * N), N - 1) still uses N --, so every row sums
+ * to n_draw, a pattern of weight 0 is never drawn, and with n_draw = N a row is pu_boot_weights'
+ * row bit for bit.  n_draws (nullable, int64 [n_rep]) gives every row its own number of columns
+ * and n_draw is then not read by the rule: one call fills rows of different scales.
+ * PU_E_ARG as pu_boot_weights, and for n_draw (without n_draws) or -- host form -- an entry of
+ * n_draws outside [1, 2^31 - 1]. */
+int pu_boot_weights_scaled(int device, uint64_t seed, int64_t first_rep, int n_rep,
+                           int64_t n_sites, const double *site_weights, int64_t n_draw,
+                           const int64_t *n_draws, uint32_t *w_out);
+/* The same on device buffers, as pu_boot_weights_device; d_n_draws (nullable) is a device
+ * buffer, and with it a positive n_draw only sizes the launch (the longest row).  Precondition:
+ * every entry of d_n_draws lies in [1, 2^31 - 1] (a row whose entry does not stays zero). */
+int pu_boot_weights_scaled_device(int device, void *stream, uint64_t seed, int64_t first_rep,
+                                  int n_rep, int64_t n_sites, const double *d_site_weights,
+                                  int64_t n_draw, const int64_t *d_n_draws, uint32_t *d_w,
+                                  int64_t ldw);
 /* The pair count matrices of every replicate in one pass over the alignment: counts_out
  * [n_rep][n_pairs][n_codes][n_codes] fp64, N[r][p][u][v] = the sum of W[r][s] over the sites
  * where pairs[p]'s first taxon shows code u and its second code v.  W uint32 [n_rep][n_sites];
@@ -798,6 +815,46 @@ int pu_bootstrap_nj(int device, int method, int n_states, int n_cat, int n_codes
  * caps the replicates of a chunk as PU_DIST_CHUNK caps the pairs; no result depends on either. */
 int pu_boot_profile(int device, int on);
 int pu_boot_kernel_ms(int device, double *counts_ms, double *newton_ms);
+
+/* ---- topology tests of candidate trees (normative) ----------------------------
+ * The replicate counts behind RELL bootstrap proportions (Kishino et al. 1990), the KH test
+ * (Kishino & Hasegawa 1989), the SH test (Shimodaira & Hasegawa 1999), expected likelihood
+ * weights (Strimmer & Rambaut 2002) and the multiscale bootstrap of the AU test (Shimodaira
+ * 2002).  The reference has no topology test: the rule is DESIGN 4.24's and
+ * tests/topotest_reference.py restates it.
+ * L fp64 [T][S]: the unweighted per-pattern lnL of T trees; site_weights [S]: non-negative
+ * integers, N = their sum in [1, 2^31 - 1]; scales [K]: r_1 .. r_K.  Block 0 draws n_0 = N
+ * columns, block k >= 1 n_k = floor(r_k N + 0.5) (two fp64 roundings); replicate i < R of block k
+ * is replicate first_rep + k R + i of pu_boot_weights_scaled's rule with n_draw = n_k, so block 0
+ * holds pu_boot_weights' rows.  B[r][t] = pu_rell_sums(W[r], L[t]), l_t = B(w, L[t]) with w the
+ * weights as a uint32 row.  A tree whose l_t is not finite is excluded: it enters no argmax or
+ * max (its l and c count as -inf) and all its counts are 0.  c_t[r] = B[r][t] - l_t.
+ *   counts_out uint32 [K + 1][3][T]:
+ *     [k][0][t] = #{r of block k : t = argmax_u B[r][u], ties to the lowest t}
+ *     [0][1][t] = #{r of block 0 : c_u*[r] - c_t[r] >= l_u* - l_t},  u* = argmax_{u != t} l_u,
+ *                 ties to the lowest u                                               (KH)
+ *     [0][2][t] = #{r of block 0 : max_u c_u[r] - c_t[r] >= max_u l_u - l_t}         (SH)
+ *     [k][1], [k][2] = 0 for k > 0
+ *   lnl_out [T] = l;  n_draw_out int64 [K + 1] = n;  rell_out (nullable) [K + 1][R][T] = B.
+ * Every compared value is a single fp64 subtraction and the counts are integers, so no result
+ * depends on the launch shape or on the ranges of rows the call walks (256 MiB of W at most;
+ * PU_TOPO_REP_CHUNK, read at each call, caps the rows of a range).  Stateless; everything is
+ * freed on return.
+ * PU_E_ARG, before any device is touched, the message naming the argument: a null buffer, T
+ * outside [2, 1024], S < 1, R < 1, K < 0, a scale that is not finite and positive or whose n_k
+ * is outside [1, 2^31 - 1], a weight that is negative, non-integer or non-finite, N outside
+ * [1, 2^31 - 1], first_rep < 0 or first_rep + (K + 1) R > 2^32.  PU_E_NOMEM (the message names
+ * the bytes) where a buffer does not fit. */
+int pu_topology_tests(int device, int T, int64_t S, const double *L, const double *site_weights,
+                      uint64_t seed, int64_t first_rep, int R, int K, const double *scales,
+                      uint32_t *counts_out, double *lnl_out, int64_t *n_draw_out,
+                      double *rell_out);
+/* Event timing of its three stages (scripts/time_topotest.py), as pu_boot_profile: with
+ * pu_topotest_profile(device, 1) every pu_topology_tests call records events round the stages of
+ * each range; pu_topotest_kernel_ms waits for the last call's and returns the time of its weight
+ * launches, of its RELL sums and of its k_topo_counts launches, in ms, summed over the ranges. */
+int pu_topotest_profile(int device, int on);
+int pu_topotest_kernel_ms(int device, double *weights_ms, double *rell_ms, double *counts_ms);
 
 /* ---- Fitch parsimony (normative) ---------------------------------------------
  * The reference has no parsimony, so there is no reference interface to cite: the rule is

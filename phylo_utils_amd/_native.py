@@ -145,6 +145,10 @@ SIGNATURES = {
     "pu_boot_weights": (_c_int, [_c_int, _c_u64, _c_i64, _c_int, _c_i64, _P, _P]),
     "pu_boot_weights_device": (_c_int, [_c_int, _P, _c_u64, _c_i64, _c_int, _c_i64, _P, _P,
                                         _c_i64]),
+    "pu_boot_weights_scaled": (_c_int, [_c_int, _c_u64, _c_i64, _c_int, _c_i64, _P, _c_i64, _P,
+                                        _P]),
+    "pu_boot_weights_scaled_device": (_c_int, [_c_int, _P, _c_u64, _c_i64, _c_int, _c_i64, _P,
+                                               _c_i64, _P, _P, _c_i64]),
     "pu_boot_pair_counts": (_c_int, [_c_int, _P, _c_int, _c_i64, _c_int, _P, _c_int, _c_i64, _P,
                                      _P]),
     "pu_boot_distances": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P,
@@ -161,6 +165,10 @@ SIGNATURES = {
                                  _c_dbl, _c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pu_boot_profile": (_c_int, [_c_int, _c_int]),
     "pu_boot_kernel_ms": (_c_int, [_c_int, _P, _P]),
+    "pu_topology_tests": (_c_int, [_c_int, _c_int, _c_i64, _P, _P, _c_u64, _c_i64, _c_int, _c_int,
+                                   _P, _P, _P, _P, _P]),
+    "pu_topotest_profile": (_c_int, [_c_int, _c_int]),
+    "pu_topotest_kernel_ms": (_c_int, [_c_int, _P, _P, _P]),
     "pu_fitch_lengths": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _c_int, _P,
                                   _P, _P, _P, _P]),
     "pu_fitch_insert_lengths": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _P,

@@ -15,7 +15,9 @@
 //     s = the first pattern whose inclusive integer prefix sum of w exceeds c
 //     W[r][s] += 1                                      uint32
 // The counts are integers: W does not depend on the grid, the order of the adds or on which
-// other replicates the call asked for.  Replicate r's pair count matrices are
+// other replicates the call asked for.  The scaled form (pu_boot_weights_scaled[_device], DESIGN
+// 4.24) is the same rule with j = 0..n_draw-1 -- c still uses N --, so a row sums to n_draw and
+// with n_draw = N it is the row above, bit for bit.  Replicate r's pair count matrices are
 //     N_ab^(r)[u][v] = sum_s W[r][s] [code_a(s) = u][code_b(s) = v],
 // integers again, so they are exact and equal, bit for bit, to what pu_pair_counts gives for
 // site_weights = W[r]; the Newton step (pu_distance.hip k_pair_newton, unchanged) and the
@@ -29,7 +31,8 @@
 //                       1024 partial sums, each thread then writes its range.
 //   k_boot_weights      one lane per (replicate, column): the draw, a binary search of the prefix
 //                       sums (none for unit weights: s = c) and a 32-bit atomic add into
-//                       W [n_rep][ldw].  Grid-stride: the grid does not need N on the host.
+//                       W [n_rep][ldw].  Grid-stride: the grid does not need N on the host.  The
+//                       number of columns is N, one n_draw for the launch or one per row.
 //   k_boot_pair_counts  k_pair_counts with lane = replicate in place of lane = pair.  A
 //                       workgroup owns P pairs (one wave each), a tile of T <= 64 replicates and
 //                       a segment of the sites.  It stages 128-site chunks of the pairs' code
@@ -129,6 +132,8 @@ struct WeightArgs {
     const int64_t *total;    // N (with prefix)
     uint32_t *W;             // [n_rep][ldw], zeroed
     int64_t ldw;
+    int64_t n_draw;          // columns of every row; 0: N
+    const int64_t *n_draws;  // [n_rep] columns of each row, or null: n_draw
 };
 
 __global__ void __launch_bounds__(256) k_boot_weights(WeightArgs a) {
@@ -137,7 +142,9 @@ __global__ void __launch_bounds__(256) k_boot_weights(WeightArgs a) {
     const double dN = (double)N;
     for (int r = (int)blockIdx.y; r < a.n_rep; r += (int)gridDim.y) {
         uint32_t *row = a.W + (int64_t)r * a.ldw;
-        for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < N;
+        const int64_t n = a.n_draws ? a.n_draws[r] : a.n_draw > 0 ? a.n_draw : N;
+        if (n > kMaxN) continue;  // outside the rule: the row stays zero
+        for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n;
              j += (int64_t)gridDim.x * 256) {
             const double u = philox_u(a.seed, (uint64_t)j, a.first_rep + (uint32_t)r, 1u);
             int64_t c = (int64_t)__dmul_rn(u, dN);
@@ -373,9 +380,11 @@ int check_reps(const char *fn, int64_t first_rep, int n_rep, int64_t n_sites) {
 }
 
 // W of n_rep replicates queued on st; N_host: N when the host knows it (unit weights, host
-// forms), else 0
+// forms), else 0; n_draw columns per row (0: N), or d_n_draws [n_rep] of them (device), n_draw
+// then only sizing the grid
 int run_weights(int device, hipStream_t st, uint64_t seed, int64_t first_rep, int n_rep,
-                int64_t S, const double *d_w, int64_t N_host, uint32_t *d_W, int64_t ldw) {
+                int64_t S, const double *d_w, int64_t N_host, uint32_t *d_W, int64_t ldw,
+                int64_t n_draw = 0, const int64_t *d_n_draws = nullptr) {
     BootState &B = g_boot[device];
     StateScope scope(B, st);
     int rc;
@@ -390,6 +399,8 @@ int run_weights(int device, hipStream_t st, uint64_t seed, int64_t first_rep, in
     a.total = nullptr;
     a.W = d_W;
     a.ldw = ldw;
+    a.n_draw = n_draw;
+    a.n_draws = d_n_draws;
     if (d_w) {
         if ((rc = B.prefix.reserve((size_t)S))) return rc;
         if ((rc = B.total.reserve(1))) return rc;
@@ -398,7 +409,7 @@ int run_weights(int device, hipStream_t st, uint64_t seed, int64_t first_rep, in
         a.prefix = B.prefix.p;
         a.total = B.total.p;
     }
-    const int64_t cols = N_host > 0 ? N_host : S;
+    const int64_t cols = std::max(N_host > 0 ? N_host : S, n_draw);
     const dim3 grid((unsigned)std::min<int64_t>(1024, (cols + 255) / 256),
                     (unsigned)std::min(n_rep, 64));
     hipLaunchKernelGGL(k_boot_weights, grid, dim3(256), 0, st, a);
@@ -603,6 +614,63 @@ int pu_boot_weights(int device, uint64_t seed, int64_t first_rep, int n_rep, int
     uint32_t *d_W = h.alloc<uint32_t>(nW);
     if (!h.rc)
         h.rc = run_weights(device, h.st, seed, first_rep, n_rep, n_sites, d_sw, N, d_W, n_sites);
+    h.to_host(w_out, d_W, nW);
+    return h.finish(fn);
+}
+
+int pu_boot_weights_scaled_device(int device, void *stream, uint64_t seed, int64_t first_rep,
+                                  int n_rep, int64_t n_sites, const double *d_site_weights,
+                                  int64_t n_draw, const int64_t *d_n_draws, uint32_t *d_w,
+                                  int64_t ldw) {
+    const char *fn = "pu_boot_weights_scaled_device";
+    int rc;
+    if (!d_w) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
+    if ((rc = check_reps(fn, first_rep, n_rep, n_sites))) return rc;
+    if (ldw < n_sites)
+        return set_err(nullptr, PU_E_ARG, "%s: row stride %lld below n_sites = %lld", fn,
+                       (long long)ldw, (long long)n_sites);
+    if (!d_site_weights && n_sites > kMaxN)
+        return set_err(nullptr, PU_E_ARG, "%s: N = %lld is outside [1, 2^31 - 1]", fn,
+                       (long long)n_sites);
+    if (!d_n_draws && (n_draw < 1 || n_draw > kMaxN))
+        return set_err(nullptr, PU_E_ARG, "%s: n_draw = %lld is outside [1, 2^31 - 1]", fn,
+                       (long long)n_draw);
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard g(device);
+    return run_weights(device, (hipStream_t)stream, seed, first_rep, n_rep, n_sites,
+                       d_site_weights, d_site_weights ? 0 : n_sites, d_w, ldw,
+                       std::max<int64_t>(n_draw, 0), d_n_draws);
+}
+
+int pu_boot_weights_scaled(int device, uint64_t seed, int64_t first_rep, int n_rep,
+                           int64_t n_sites, const double *site_weights, int64_t n_draw,
+                           const int64_t *n_draws, uint32_t *w_out) {
+    const char *fn = "pu_boot_weights_scaled";
+    int rc;
+    int64_t N = 0, most = n_draw;
+    if (!w_out) return set_err(nullptr, PU_E_ARG, "%s: null output", fn);
+    if ((rc = check_reps(fn, first_rep, n_rep, n_sites))) return rc;
+    if ((rc = host_total(fn, site_weights, n_sites, &N))) return rc;
+    for (int r = 0; r < (n_draws ? n_rep : 0); ++r) {
+        if (n_draws[r] < 1 || n_draws[r] > kMaxN)
+            return set_err(nullptr, PU_E_ARG, "%s: n_draws[%d] = %lld is outside [1, 2^31 - 1]",
+                           fn, r, (long long)n_draws[r]);
+        most = r ? std::max(most, n_draws[r]) : n_draws[r];
+    }
+    if (!n_draws && (n_draw < 1 || n_draw > kMaxN))
+        return set_err(nullptr, PU_E_ARG, "%s: n_draw = %lld is outside [1, 2^31 - 1]", fn,
+                       (long long)n_draw);
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard g(device);
+    HostCall h(device);
+    const size_t nW = (size_t)n_rep * n_sites;
+    const double *d_sw = h.to_device(site_weights, (size_t)n_sites);
+    const int64_t *d_nd = h.to_device(n_draws, (size_t)n_rep);
+    uint32_t *d_W = h.alloc<uint32_t>(nW);
+    // the grid is sized for the longest row; its stride loop covers any other
+    if (!h.rc)
+        h.rc = run_weights(device, h.st, seed, first_rep, n_rep, n_sites, d_sw, N, d_W, n_sites,
+                           most, d_nd);
     h.to_host(w_out, d_W, nW);
     return h.finish(fn);
 }

@@ -71,7 +71,15 @@ of its full length -- on the final tree without rebuilding it (``phylo_utils_amd
 query is scored at every edge, its K best edges (default 5) are refined on the pendant length,
 and OUT.jplace receives them in jplace version 3 (``edge_num, likelihood, like_weight_ratio,
 distal_length, pendant_length``); ``--placed-trees FILE`` receives one Newick per query, the tree
-with that query joined at its best placement (``-o`` stays what the other options make it).
+with that query joined at its best placement (``-o`` stays what the other options make it);
+``--test-trees FILE [--test-replicates R] [--no-au]`` tests the candidate topologies of FILE, one
+Newick per line, against each other (``phylo_utils_amd.topotest``): the final tree of the run --
+when ``-t``, ``--nj`` or ``--parsimony`` gave one; ``-s`` and ``-m`` alone do -- is tree 0, the
+trees of FILE follow, every tree's branch lengths are optimised (``--optimise`` passes, at least
+one), and after the ``lnL = `` line come a header and one line per tree, ``tree i: lnL deltaL
+bp-RELL p-KH p-SH c-ELW p-AU`` over R RELL replicates (default 10000, the seed of ``--seed``),
+every value from bp-RELL on followed by ``+`` (the tree stays in the 95 % set of that test) or
+``-`` (rejected); ``--no-au`` skips the multiscale replicates and prints p-AU as ``-``.
 """
 from __future__ import annotations
 
@@ -237,6 +245,16 @@ def parse_cli(argv=None):
     ap.add_argument("--placed-trees", type=str, default=None, metavar="FILE", dest="placed_trees",
                     help="with --place: write one Newick per query, the tree with the query "
                          "joined at its best placement")
+    ap.add_argument("--test-trees", type=str, default=None, metavar="FILE", dest="test_trees",
+                    help="test the candidate trees of FILE (one Newick per line) and the run's "
+                         "final tree (tree 0) against each other: RELL bootstrap proportions, KH, "
+                         "SH, c-ELW and AU, one line per tree after the lnL line")
+    ap.add_argument("--test-replicates", type=int, default=10000, metavar="R",
+                    dest="test_replicates",
+                    help="with --test-trees: RELL replicates per scale (default 10000; seed: "
+                         "--seed)")
+    ap.add_argument("--no-au", action="store_true", dest="no_au",
+                    help="with --test-trees: no multiscale replicates; p-AU is printed as '-'")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -260,6 +278,28 @@ def validate_args(args):
             raise ValueError("--keep needs at least one edge")
         if not os.path.exists(args.place):
             raise FileNotFoundError("Query file {} does not exist".format(args.place))
+    if getattr(args, "test_trees", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--test-trees excludes --simulate and --distances")
+        if getattr(args, "ascertainment", None):
+            raise ValueError("--test-trees with --ascertainment is not implemented")
+        if getattr(args, "test_replicates", 10000) < 1:
+            raise ValueError("--test-replicates needs at least one replicate")
+        if not os.path.exists(args.test_trees):
+            raise FileNotFoundError("Tree file {} does not exist".format(args.test_trees))
+        if args.tree is None and getattr(args, "nj", None) is None and \
+                getattr(args, "parsimony", None) is None:
+            # no tree of the run's own: the candidates alone
+            for name in ("optimise", "nni", "spr", "fit", "place", "support", "ancestral",
+                         "site_rates", "parsimony_score"):
+                if getattr(args, name, None) not in (None, 0, False):
+                    raise ValueError("--{} needs a tree (-t, --nj or --parsimony)".format(
+                        name.replace("_", "-")))
+            if args.alignment is None:
+                raise ValueError("Alignment file not specified")
+            if not os.path.exists(args.alignment):
+                raise FileNotFoundError("Alignment file {} does not exist".format(args.alignment))
+            return
     if getattr(args, "fit", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--fit excludes --simulate and --distances")
@@ -344,18 +384,23 @@ def run(args, out=None):
     nj = getattr(args, "nj", None)
     pars = getattr(args, "parsimony", None)
     pars_length = None
-    if nj is None and pars is None:
+    given = nj is None and pars is None and args.tree is not None
+    if given:
         with open(args.tree) as fh:
             tree = parse_newick(fh.read())
     aln = A.read_fasta(args.alignment)
     desc = parse_model_string(args.model)
     alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
     tm = TreeModel(device=args.device)
-    if nj is None and pars is None:
+    if given:
         tm.set_tree(tree)
     tm.set_alignment(aln, alphabet)
     tm.set_rate_model(build_rate_model(desc))
     tm.set_substitution_model(build_model(desc))
+    if nj is None and pars is None and not given:  # --test-trees on its candidates alone
+        for line in run_test_trees(args, tm, None):
+            out.write(line + "\n")
+        return None
     if nj is not None:  # --nj: the tree from the alignment's own distances
         if getattr(args, "bootstrap", None) is not None:
             tree, _, _ = tm.bootstrap_nj(args.bootstrap, seed=args.seed, method=nj)
@@ -439,13 +484,34 @@ def run(args, out=None):
             fh.write("site\tmean_rate\tmap_category\n")
             for i, (r, k) in enumerate(zip(rate, cat.argmax(axis=1))):
                 fh.write("{}\t{:.10g}\t{}\n".format(i + 1, r, int(k) + 1))
+    table = []
+    if getattr(args, "test_trees", None) is not None:
+        from .tree import with_lengths
+        table = run_test_trees(args, tm, with_lengths(tm.tree, tm.traversal.brlens))
     lnl = tm.compute_likelihood_at_edge(*tm.traversal.root_edge).sum()
     if pars_length is not None:
         out.write("parsimony = {}\n".format(pars_length))
     if fitted is not None:
         out.write("model = {}\n".format(fitted))
     out.write("lnL = {}\n".format(lnl))
+    for line in table:
+        out.write(line + "\n")
     return lnl
+
+
+def run_test_trees(args, tm, first):
+    """--test-trees: the table lines of ``topotest.topology_tests`` on `first` (the run's tree, or
+    None) and the trees of the file."""
+    from . import topotest
+    with open(args.test_trees) as fh:
+        trees = [line.strip() for line in fh if line.strip()]
+    if first is not None:
+        trees.insert(0, first)
+    au = not getattr(args, "no_au", False)
+    res = topotest.topology_tests(tm, trees, n_replicates=getattr(args, "test_replicates", 10000),
+                                  scales=topotest.DEFAULT_SCALES if au else (), seed=args.seed,
+                                  sweeps=max(args.optimise, 1))
+    return topotest.format_table(res, au=au)
 
 
 def run_simulate(args, out=None):

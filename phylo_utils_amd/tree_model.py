@@ -635,6 +635,17 @@ class TreeModel(object):
         return support.branch_support(self, n_replicates, seed, epsilon, tol, max_iter,
                                       first_replicate, full)
 
+    def topology_tests(self, trees, n_replicates=10000, scales=None, seed=0, optimise=True,
+                       sweeps=1):
+        """RELL bootstrap proportions, KH, SH, c-ELW and AU of the candidate `trees` on this
+        model's alignment and models (``topotest.topology_tests``, pu_topology_tests): a dict of
+        arrays [T].  `scales` None: the ten default scales of the AU test.  The model ends on the
+        tree it started on."""
+        from . import topotest
+        return topotest.topology_tests(
+            self, trees, n_replicates, topotest.DEFAULT_SCALES if scales is None else scales, seed,
+            optimise, sweeps)
+
     # ------------------------------------------------------------------ ancestral states
     def ancestral_states(self, full=False):
         """The most probable state of every internal node at every pattern, its posterior and,
