@@ -20,9 +20,8 @@
 //
 // Mapping (k_edge's): a workgroup is one 64-site tile, a lane a site, wave w owns
 // rate categories w, w + nw, ...; the categories of a site meet in LDS, where wave 0 mixes them.
-// P_c(t) is built once per workgroup into LDS from the eigen-system with build_p's arithmetic.
 // Every sum runs in a fixed order (categories ascending, states ascending); every workgroup
-// writes its weighted lnL sum and a one-workgroup second launch adds them in k_edge_sum's order.
+// writes its weighted lnL sum and a one-workgroup second launch adds them (k_tile_sums).
 #include <math.h>
 
 #include <cmath>
@@ -50,17 +49,12 @@ struct AncArgs {
 constexpr int kAncMaxWaves = 8;
 __host__ __device__ inline int anc_waves(int C) { return C < kAncMaxWaves ? C : kAncMaxWaves; }
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][exponentials
-// C*K][P C*K*K][per (category, site): g(0..K-1), F, sigma -- later the mix weight: C*(K+2)*64]
-struct AncLds {
-    size_t evecs, ivecs, evals, pi, rates, ex, P, vals, total;
-    __host__ __device__ AncLds(int K, int C) {
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        pi = evals + K;
-        rates = pi + K;
-        ex = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+// LDS of one workgroup (doubles): the model (ModelLds), then [exponentials C*K][P C*K*K][per
+// (category, site): g(0..K-1), F, sigma -- later the mix weight: C*(K+2)*64]
+struct AncLds : ModelLds {
+    size_t ex, P, vals, total;
+    __host__ __device__ AncLds(int K, int C) : ModelLds(K, C) {
+        ex = body;
         P = ex + (size_t)C * K;
         vals = P + (size_t)C * K * K;
         total = vals + (size_t)C * (K + 2) * kLanes;
@@ -81,32 +75,11 @@ __global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, Anc
     double *vals = lds + L.vals;
     constexpr int kRow = (K + 2) * kLanes;  // doubles per category in vals
 
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-        lds[L.evecs + i] = a.evecs[i];
-        lds[L.ivecs + i] = a.ivecs[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        lds[L.evals + i] = a.evals[i];
-        lds[L.pi + i] = a.pi[i];
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    load_model<K>(a, lds, L);
     __syncthreads();
-    // P_c(t) = evecs diag(e^{lambda (t r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
-    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
-        const int k = idx % K, c = idx / K;
-        lds[L.ex + idx] = exp(el[k] * (q.t * rt[c]));
-    }
+    exp_tables<K>(lds + L.ex, el, rt, C, 1, &q.t);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
-        const int ij = idx % (K * K), c = idx / (K * K);
-        const int i = ij / K, j = ij - i * K;
-        const double *e = ex + c * K;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        // an invariable category (rate 0): P = I itself, as the traversal builds it
-        lds[L.P + idx] = rt[c] == 0.0 ? (i == j ? 1.0 : 0.0) : acc;
-    }
+    p_tables<K, true>(lds + L.P, ev, iv, ex, rt, C);
     __syncthreads();
 
     // K = 20: the rows of P are read from LDS where they are used (unrolled, they are hoisted
@@ -138,26 +111,12 @@ __global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, Anc
     __syncthreads();
     if (w != 0) return;
 
-    // wave 0 mixes the categories of its 64 sites.  Only categories with F_c > 0 take part
-    // (k_edge's rule: an all-zero vector keeps an unrescaled scaler, which must not set m)
+    // wave 0 mixes the categories of its 64 sites; the mix weight replaces sigma_c
     double v0 = 0.0;
     if (site < a.S) {
         double *vs = vals + l;
-        double m = -INFINITY;
-        for (int c = 0; c < C; ++c)
-            if (vs[(size_t)c * kRow + K * kLanes] > 0.0)
-                m = fmax(m, vs[(size_t)c * kRow + (K + 1) * kLanes]);
-        double Z = 0.0;
-        for (int c = 0; c < C; ++c) {
-            const double F = vs[(size_t)c * kRow + K * kLanes];
-            double we = 0.0;
-            if (F > 0.0) {
-                const double sc = vs[(size_t)c * kRow + (K + 1) * kLanes];
-                we = a.weights[c] * (sc == m ? 1.0 : exp(sc - m));
-            }
-            vs[(size_t)c * kRow + (K + 1) * kLanes] = we;  // the mix weight replaces sigma_c
-            Z += we * F;
-        }
+        const double m = mix_max(vs + K * kLanes, vs + (K + 1) * kLanes, kRow, C);
+        const double Z = mix_weights(vs + K * kLanes, vs + (K + 1) * kLanes, kRow, C, a.weights, m);
         int best = 0;
         double bestq = 0.0;
         dbl2 *post = q.post ? reinterpret_cast<dbl2 *>(q.post + (size_t)site * K) : nullptr;
@@ -194,42 +153,17 @@ __global__ void __launch_bounds__(64 * kAncMaxWaves) k_ancestral(EdgeArgs a, Anc
             }
             if (q.mean_rate) q.mean_rate[site] = mr;
         }
-        const double pw = a.pattern_w[site];
-        if (Z > 0.0)
-            v0 = pw * (m + log(Z));
-        else if (pw != 0.0)
-            v0 = -INFINITY;  // every category has F = 0 (lnl_node's -inf)
+        v0 = mix_lnl(a.pattern_w[site], m, Z);
     }
     v0 = wave_sum(v0);
     if (l == 0) q.part[blockIdx.x] = v0;
-}
-
-// second launch: the workgroups' sums in a fixed order (k_edge_sum's: partial b by thread
-// b % 256, a 64-lane tree, the four waves in order)
-__global__ void __launch_bounds__(256) k_ancestral_sum(const double *__restrict__ part, int n,
-                                                       double *__restrict__ result) {
-    __shared__ double red[4];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < n; b += blockDim.x) s += part[b];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = 0.0;
-        for (int k = 0; k < 4; ++k) r += red[k];
-        *result = r;
-    }
 }
 
 size_t anc_lds_bytes(int K, int C) { return AncLds(K, C).total * sizeof(double); }
 
 // the largest C whose P matrices and mix area fit the LDS of a CU, and a context can hold
 // (K = 2: 64, 4: 50, 20: 10)
-int anc_max_cat(int K) {
-    int C = 0;
-    while (C < kCtxMaxCat && anc_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
-    return C;
-}
+int anc_max_cat(int K) { return max_cat(K, anc_lds_bytes); }
 
 bool is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
 
@@ -253,15 +187,11 @@ int ancestral_enqueue(pu_ctx *c, AncArgs q, double *lnl_dev) {
     q.part = c->d_a_part;
     int rc;
     if ((rc = c->a_timer.begin(c))) return rc;
-    switch (c->K) {
-        case 2: launch_ancestral_k<2>(c->stream, a, q); break;
-        case 4: launch_ancestral_k<4>(c->stream, a, q); break;
-        default: launch_ancestral_k<20>(c->stream, a, q); break;
-    }
+    dispatch_k(c->K, [&](auto k) { launch_ancestral_k<k()>(c->stream, a, q); });
     HIPCHK(&c->err, hipGetLastError());
     if ((rc = c->a_timer.end(c))) return rc;
-    hipLaunchKernelGGL(k_ancestral_sum, dim3(1), dim3(256), 0, c->stream, c->d_a_part,
-                       c->n_tiles, lnl_dev);
+    hipLaunchKernelGGL(k_tile_sums<1>, dim3(1), dim3(256), 0, c->stream, c->d_a_part, c->n_tiles,
+                       lnl_dev, 0.0);
     HIPCHK(&c->err, hipGetLastError());
     return PU_OK;
 }
@@ -271,10 +201,7 @@ int ancestral_enqueue(pu_ctx *c, AncArgs q, double *lnl_dev) {
 extern "C" {
 
 int pu_ancestral_max_cat(int n_states) {
-    if (n_states != 2 && n_states != 4 && n_states != 20)
-        return set_err(nullptr, PU_E_ARG, "pu_ancestral_max_cat: K=%d is not supported",
-                       n_states);
-    return anc_max_cat(n_states);
+    return max_cat_call("pu_ancestral_max_cat", n_states, anc_max_cat);
 }
 
 int pu_ancestral_edge(pu_ctx *c, int node, int other, double length, uint8_t *map_state,

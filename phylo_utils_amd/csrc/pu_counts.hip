@@ -19,9 +19,8 @@
 //
 // Mapping: a workgroup takes tiles b, b + G, b + 2G, ... of 64 sites (G workgroups, a function
 // of the tile count alone), a lane a site, wave w owns rate categories w, w + nw, ...  Per tile
-// the first half is k_ancestral's (P_c(t) in LDS with build_p's arithmetic, y = P_c B, F_c, the
-// mix by wave 0 over the categories with F_c > 0), which leaves coef_sc = pw w_c e^{..} / Z in
-// LDS; the second half adds coef A(i) B(j).
+// the first half is k_ancestral's (y = P_c B, F_c, the mix by wave 0), which leaves coef_sc =
+// pw w_c e^{..} / Z in LDS; the second half adds coef A(i) B(j).
 //   K = 2, 4: a lane keeps the K x K sums of one category in registers across all its tiles
 //     and the wave adds them with one wave_sum per entry at the end.  More categories than
 //     waves (8; K = 20: 4) are taken in rounds, one category per wave and round; a round
@@ -33,7 +32,7 @@
 //     kept for the measurement behind it (PU_COUNTS_VALU=1 selects it).
 // Sum order: sites ascending within a lane (tiles ascending), a fixed lane tree (K <= 4) or
 // the matrix core's fixed k order (K = 20), then a one-workgroup second launch that adds the
-// workgroups' matrices in index order and the lnL sums in k_edge_sum's order.  Nothing depends
+// workgroups' matrices in index order and the lnL sums in tile_sums' order.  Nothing depends
 // on timing: two runs are bitwise equal.
 #include <math.h>
 #include <stdlib.h>
@@ -71,18 +70,12 @@ __host__ __device__ inline int cnt_grid(int K, int n_tiles) {
     return n_tiles < 256 ? n_tiles : 256;  // one workgroup per CU of an MI355X
 }
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][exponentials
-// C*K][P C*K*K][per category: F, sigma -- later coef: 2*64][K = 20, per category: coef A and B
-// staged [K][66] each]
-struct CntLds {
-    size_t evecs, ivecs, evals, pi, rates, ex, P, vals, stage, total;
-    __host__ __device__ CntLds(int K, int C) {
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        pi = evals + K;
-        rates = pi + K;
-        ex = (rates + C + 1) & ~size_t(1);
+// LDS of one workgroup (doubles): the model (ModelLds), then [exponentials C*K][P C*K*K][per
+// category: F, sigma -- later coef: 2*64][K = 20, per category: coef A and B staged [K][66] each]
+struct CntLds : ModelLds {
+    size_t ex, P, vals, stage, total;
+    __host__ __device__ CntLds(int K, int C) : ModelLds(K, C) {
+        ex = body;
         P = ex + (size_t)C * K;
         vals = P + (size_t)C * K * K;
         stage = vals + (size_t)C * 2 * kLanes;
@@ -103,32 +96,11 @@ __global__ void __launch_bounds__(64 * cnt_max_waves(K)) k_counts(EdgeArgs a, Cn
     constexpr int kRow = 2 * kLanes;  // doubles per category in vals: F, then sigma / coef
     constexpr int kKK = K * K;
 
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-        lds[L.evecs + i] = a.evecs[i];
-        lds[L.ivecs + i] = a.ivecs[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        lds[L.evals + i] = a.evals[i];
-        lds[L.pi + i] = a.pi[i];
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    load_model<K>(a, lds, L);
     __syncthreads();
-    // P_c(t) = evecs diag(e^{lambda (t r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
-    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
-        const int k = idx % K, c = idx / K;
-        lds[L.ex + idx] = exp(el[k] * (q.t * rt[c]));
-    }
+    exp_tables<K>(lds + L.ex, el, rt, C, 1, &q.t);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
-        const int ij = idx % (K * K), c = idx / (K * K);
-        const int i = ij / K, j = ij - i * K;
-        const double *e = ex + c * K;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        // an invariable category (rate 0): P = I itself, as the traversal builds it
-        lds[L.P + idx] = rt[c] == 0.0 ? (i == j ? 1.0 : 0.0) : acc;
-    }
+    p_tables<K, true>(lds + L.P, ev, iv, ex, rt, C);
     __syncthreads();
 
     const int n_rounds = (C + nw - 1) / nw;
@@ -192,34 +164,21 @@ __global__ void __launch_bounds__(64 * cnt_max_waves(K)) k_counts(EdgeArgs a, Cn
             }
             __syncthreads();
             if (w == 0) {
-                // wave 0 mixes the categories of its 64 sites; only categories with F_c > 0
-                // take part (k_edge's rule).  coef_c = pw w_c e^{sigma_c - m} / Z replaces
-                // sigma_c; exactly 0 where pw = 0 and past the last pattern
+                // wave 0 mixes the categories of its 64 sites.  coef_c = pw w_c e^{sigma_c - m} / Z
+                // replaces sigma_c; exactly 0 where pw = 0 and past the last pattern
                 double *vs = vals + l;
                 const double pw = site < a.S ? a.pattern_w[site] : 0.0;
-                double mx = -INFINITY;
-                for (int c = 0; c < C; ++c)
-                    if (vs[(size_t)c * kRow] > 0.0) mx = fmax(mx, vs[(size_t)c * kRow + kLanes]);
-                double Z = 0.0;
-                for (int c = 0; c < C; ++c) {
-                    const double F = vs[(size_t)c * kRow];
-                    double we = 0.0;
-                    if (F > 0.0) {
-                        const double sc = vs[(size_t)c * kRow + kLanes];
-                        we = a.weights[c] * (sc == mx ? 1.0 : exp(sc - mx));
-                    }
-                    vs[(size_t)c * kRow + kLanes] = we;
-                    Z += we * F;
-                }
+                const double mx = mix_max(vs, vs + kLanes, kRow, C);
+                const double Z = mix_weights(vs, vs + kLanes, kRow, C, a.weights, mx);
                 for (int c = 0; c < C; ++c) {
                     const double we = vs[(size_t)c * kRow + kLanes];
                     vs[(size_t)c * kRow + kLanes] = pw != 0.0 ? pw * we / Z : 0.0;
                 }
-                if (r == 0) {
+                if (r == 0) {  // mix_lnl's rule, written out: the product contracts into the sum
                     if (Z > 0.0)
                         lnl_acc += pw * (mx + log(Z));
                     else if (pw != 0.0)
-                        lnl_acc = -INFINITY;  // every category has F = 0 (lnl_node's -inf)
+                        lnl_acc = -INFINITY;
                 }
             }
             __syncthreads();
@@ -322,39 +281,23 @@ __global__ void __launch_bounds__(64 * cnt_max_waves(K)) k_counts(EdgeArgs a, Cn
 }
 
 // second launch, one workgroup: entry e of the result is the workgroups' entries e added in
-// index order; the lnL is their sums in k_edge_sum's order (partial b by thread b % 256, a
-// 64-lane tree, the four waves in order)
+// index order; the lnL is their sums in tile_sums' order
 __global__ void __launch_bounds__(256) k_counts_sum(const double *__restrict__ part, int n,
                                                     int n_entries, double *__restrict__ counts,
                                                     double *__restrict__ lnl) {
-    __shared__ double red[4];
     for (int e = threadIdx.x; e < n_entries; e += blockDim.x) {
         double s = 0.0;
         for (int b = 0; b < n; ++b) s += part[(size_t)b * n_entries + e];
         counts[e] = s;
     }
-    const double *lp = part + (size_t)n * n_entries;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < n; b += blockDim.x) s += lp[b];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = 0.0;
-        for (int k = 0; k < 4; ++k) r += red[k];
-        *lnl = r;
-    }
+    tile_sums<1>(part + (size_t)n * n_entries, n, lnl);
 }
 
 size_t cnt_lds_bytes(int K, int C) { return CntLds(K, C).total * sizeof(double); }
 
 // the largest C whose tables fit the LDS of a CU and a context can hold (K = 2: 64, 4: 64,
 // 20: 6)
-int cnt_max_cat(int K) {
-    int C = 0;
-    while (C < kCtxMaxCat && cnt_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
-    return C;
-}
+int cnt_max_cat(int K) { return max_cat(K, cnt_lds_bytes); }
 
 size_t cnt_part_doubles(const pu_ctx *c) {
     return (size_t)cnt_grid(c->K, c->n_tiles) * ((size_t)c->C * c->K * c->K + 1);
@@ -390,16 +333,12 @@ int counts_enqueue(pu_ctx *c, CntArgs q, double *counts_dev, double *lnl_dev) {
     q.part = c->d_c_part;
     int rc;
     if ((rc = c->c_timer.begin(c))) return rc;
-    switch (c->K) {
-        case 2: launch_counts_k<2, false>(c->stream, a, q); break;
-        case 4: launch_counts_k<4, false>(c->stream, a, q); break;
-        default:
-            if (counts_valu())
-                launch_counts_k<20, false>(c->stream, a, q);
-            else
-                launch_counts_k<20, true>(c->stream, a, q);
-            break;
-    }
+    dispatch_k(c->K, [&](auto k) {
+        if constexpr (k() == 20) {
+            if (!counts_valu()) return launch_counts_k<20, true>(c->stream, a, q);
+        }
+        launch_counts_k<k(), false>(c->stream, a, q);
+    });
     HIPCHK(&c->err, hipGetLastError());
     if ((rc = c->c_timer.end(c))) return rc;
     hipLaunchKernelGGL(k_counts_sum, dim3(1), dim3(256), 0, c->stream, c->d_c_part,
@@ -413,9 +352,7 @@ int counts_enqueue(pu_ctx *c, CntArgs q, double *counts_dev, double *lnl_dev) {
 extern "C" {
 
 int pu_counts_max_cat(int n_states) {
-    if (n_states != 2 && n_states != 4 && n_states != 20)
-        return set_err(nullptr, PU_E_ARG, "pu_counts_max_cat: K=%d is not supported", n_states);
-    return cnt_max_cat(n_states);
+    return max_cat_call("pu_counts_max_cat", n_states, cnt_max_cat);
 }
 
 int pu_edge_counts(pu_ctx *c, int node, int other, double length, double *counts_out,

@@ -245,13 +245,13 @@ int run_reduce(pu_ctx *c, int mode, const NodeSrc &sa, const NodeSrc &sb, double
     }
     // EDGE_DERIV: every workgroup writes its 3 partial sums straight into pinned host memory
     // and the host adds them in workgroup order once every slot has left the sentinel
-    // (PU_EDGE_HOST_SUM=0: the k_edge_sum launch below)
+    // (PU_EDGE_HOST_SUM=0: the k_tile_sums launch below)
     const int host_sum_env = env_int("PU_EDGE_HOST_SUM", 1);
     if (host_sum_env && mode == EDGE_DERIV && a.two_pass == 1) {
         const int b = c->edge_part_buf ^= 1;
         double *hp = c->h_edge_part[b];
         a.block_part = c->d_edge_part_host[b];
-        a.two_pass = 2;  // partials only, no k_edge_sum
+        a.two_pass = 2;  // partials only, no k_tile_sums
         const size_t n = 3 * (size_t)c->n_tiles;
         // every way out of here leaves the buffer sentinel-filled again: a stale value left in
         // it would pass for a result two evaluations later
@@ -290,7 +290,7 @@ int run_reduce(pu_ctx *c, int mode, const NodeSrc &sa, const NodeSrc &sb, double
         r3[2] = s2;
         return PU_OK;
     }
-    // Completion: the host polls the sequence number k_edge_sum writes into mapped memory
+    // Completion: the host polls the sequence number k_tile_sums writes into mapped memory
     // after the sums (PU_EDGE_POLL=0: hipStreamSynchronize).  Not with the ascertainment
     // correction, which rewrites the lnL in a later launch.
     const int poll_env = env_int("PU_EDGE_POLL", 1);

@@ -74,18 +74,14 @@ constexpr int kMaxWaves = 8;
 __host__ __device__ inline int edge_waves(int C) { return C < kMaxWaves ? C : kMaxWaves; }
 __host__ __device__ inline int edge_mats(int mode) { return mode == EDGE_DERIV ? 4 : 2; }
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][rates C][P matrices
+// LDS of one workgroup (doubles): the model without pi (ModelLds), then [P matrices
 // n_mat*C*K*K][exp workspace n_mat*C*K][per-(category, site) values: C*64*(1 | 4)][wave
 // partial sums 3*kMaxWaves]
-struct EdgeLds {
-    size_t evecs, ivecs, evals, rates, P, ex, vals, red, total;
-    __host__ __device__ EdgeLds(int mode, int K, int C) {
+struct EdgeLds : ModelLds {
+    size_t P, ex, vals, red, total;
+    __host__ __device__ EdgeLds(int mode, int K, int C) : ModelLds(K, C, false) {
         const int nm = edge_mats(mode);
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        rates = evals + K;
-        P = (rates + C + 1) & ~size_t(1);  // 16-byte aligned matrices
+        P = body;
         ex = P + (size_t)nm * C * K * K;
         vals = ex + (size_t)nm * C * K;
         red = vals + (mode == EDGE_UPDATE ? 0 : (size_t)C * 64 * (mode == EDGE_DERIV ? 4 : 1));
@@ -101,8 +97,8 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // P matrices into LDS: n_mat matrices per category, matrix m of category c at
-// P[(m * C + c) * K * K].  Matrix m uses length t[m] and derivative order ord[m]:
-// evecs diag(x^ord e^{l t r}) ivecs with x = l r (k_pmatrix's arithmetic for ord 0).
+// P[(m * C + c) * K * K].  Matrix m uses length t[m] and derivative order ord[m] (exp_tables,
+// p_tables; the derivatives of a rate-0 category are exactly 0 already, x = 0).
 template <int K>
 __device__ void build_p(const EdgeArgs &a, double *lds, const EdgeLds &L, int n_mat,
                         const double (&t)[4], const int (&ord)[4], const double *host = nullptr) {
@@ -115,31 +111,9 @@ __device__ void build_p(const EdgeArgs &a, double *lds, const EdgeLds &L, int n_
     }
     const double *ev = lds + L.evecs, *iv = lds + L.ivecs, *el = lds + L.evals,
                  *rt = lds + L.rates;
-    double *ex = lds + L.ex, *P = lds + L.P;
-    for (int idx = threadIdx.x; idx < n_mat * C * K; idx += nt) {
-        const int k = idx % K, mc = idx / K, c = mc % C, m = mc / C;
-        const double r = rt[c];
-        const double tt = t[m] * r;
-        double e = exp(el[k] * tt);
-        if (ord[m] > 0) {
-            const double x = el[k] * r;
-            e = ord[m] == 1 ? x * e : (x * x) * e;
-        }
-        ex[idx] = e;
-    }
+    exp_tables<K>(lds + L.ex, el, rt, C, n_mat, t, ord);
     lds_barrier();
-    for (int idx = threadIdx.x; idx < n_mat * C * K * K; idx += nt) {
-        const int ij = idx % (K * K), mc = idx / (K * K);
-        const int i = ij / K, j = ij - i * K;
-        const double *e = ex + mc * K;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        // an invariable category (rate 0): P = I itself, as the traversal builds it (DESIGN
-        // 4.21); its derivatives are exactly 0 already (x = 0)
-        const int c = mc % C, m = mc / C;
-        P[idx] = (rt[c] == 0.0 && ord[m] == 0) ? (i == j ? 1.0 : 0.0) : acc;
-    }
+    p_tables<K, true>(lds + L.P, ev, iv, lds + L.ex, rt, C, n_mat, ord);
     lds_barrier();
 }
 
@@ -237,12 +211,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_edge(EdgeArgs a) {
     // P(t_a), P(t_b) of each of at most two ops -- read through the scalar unit
     const bool inline_p = K <= 4 && a.inline_p && MODE != EDGE_LNL;
     if (!late_model && !inline_p) {
-        for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-            lds[L.evecs + i] = a.evecs[i];
-            lds[L.ivecs + i] = a.ivecs[i];
-        }
-        for (int i = threadIdx.x; i < K; i += blockDim.x) lds[L.evals + i] = a.evals[i];
-        for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+        load_model<K, false>(a, lds, L);
         __syncthreads();  // (nothing is in flight yet)
     }
 
@@ -371,35 +340,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_edge(EdgeArgs a) {
                 a.site_lnl[site] = sl;
                 v0 = pw * sl;
             } else {
-                // per site: L = sum_c w_c f_c e^{s_c} = e^smax sum_c w_c f_c e^{s_c - smax}
-                // (s_c = sa + sb, the category's log scaler: equal across categories unless a
-                // child was rescaled, so the exponential is usually skipped), and
-                // dlnL/dt = sum_c w_c f'_c e^{..} / sum_c w_c f_c e^{..}, likewise d2.
-                // Only categories with f_c > 0 take part (lnl_node's -inf for the others,
-                // numba_likelihood_engine.py:82-87): an all-zero CLV keeps an unrescaled
-                // scaler, which must not set smax and underflow every other category's
-                // weight (e.g. an invariant category under host matrices, P(0) = I)
-                double smax = -INFINITY;
-                for (int c = 0; c < C; ++c)
-                    if (vals[c * kLanes + l] > 0.0)
-                        smax = fmax(smax, vals[(3 * C + c) * kLanes + l]);
-                double Ls = 0.0, N1 = 0.0, N2 = 0.0;
-                for (int c = 0; c < C; ++c) {
-                    if (!(vals[c * kLanes + l] > 0.0)) continue;
-                    const double sc = vals[(3 * C + c) * kLanes + l];
-                    const double we = a.weights[c] * (sc == smax ? 1.0 : exp(sc - smax));
-                    Ls += we * vals[c * kLanes + l];
-                    N1 += we * vals[(C + c) * kLanes + l];
-                    N2 += we * vals[(2 * C + c) * kLanes + l];
-                }
-                if (Ls > 0.0) {
-                    const double d1 = N1 / Ls;
-                    v0 = pw * (smax + log(Ls));
-                    v1 = pw * d1;
-                    v2 = pw * (N2 / Ls - d1 * d1);
-                } else if (pw != 0.0) {
-                    v0 = -INFINITY;  // every category has f = 0 (lnl_node's -inf)
-                }
+                mix_derivs(vals + l, C, a.weights, pw, v0, v1, v2);
             }
         }
         // workgroup sum = wave 0's sum (the other waves contribute 0)
@@ -408,7 +349,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_edge(EdgeArgs a) {
             v1 = wave_sum(v1);
             v2 = wave_sum(v2);
         }
-        if (a.two_pass) {  // partials only; k_edge_sum adds them (second launch)
+        if (a.two_pass) {  // partials only; k_tile_sums<3> adds them (second launch)
             if (threadIdx.x == 0) {
                 double *p = a.block_part + 3 * (size_t)blockIdx.x;
                 p[0] = v0;
@@ -418,45 +359,6 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_edge(EdgeArgs a) {
             return;
         }
         grid_reduce3(a, lds + L.red, v0, v1, v2);
-    }
-}
-
-// second launch of the two-pass reduction: the same fixed order as grid_reduce3
-__global__ void __launch_bounds__(256) k_edge_sum(const double *__restrict__ part, int n,
-                                                  double *__restrict__ result, double seq) {
-    __shared__ double red[3 * 4];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int b = threadIdx.x; b < n; b += blockDim.x) {
-        s0 += part[3 * b];
-        s1 += part[3 * b + 1];
-        s2 += part[3 * b + 2];
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[3 * w] = s0;
-        red[3 * w + 1] = s1;
-        red[3 * w + 2] = s2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-        for (int k = 0; k < 4; ++k) {
-            r0 += red[3 * k];
-            r1 += red[3 * k + 1];
-            r2 += red[3 * k + 2];
-        }
-        result[0] = r0;
-        result[1] = r1;
-        result[2] = r2;
-        if (seq != 0.0) {
-            // the host polls result[3] (mapped memory) instead of synchronising the stream:
-            // the sums reach host memory before the sequence number does
-            __threadfence_system();
-            __hip_atomic_store(result + 3, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 
@@ -955,8 +857,10 @@ int launch_edge_k(hipStream_t st, int mode, const EdgeArgs &a, size_t lds,
         default: return (int)hipErrorInvalidValue;
     }
     if (after_edge) (void)hipEventRecord(after_edge, st);
-    if (mode != EDGE_UPDATE && a.two_pass == 1)  // 2: the host adds the partials
-        hipLaunchKernelGGL(k_edge_sum, dim3(1), dim3(256), 0, st, a.block_part, a.n_tiles,
+    // the second launch of the two-pass reduction (2: the host adds the partials): the same
+    // fixed order as grid_reduce3
+    if (mode != EDGE_UPDATE && a.two_pass == 1)
+        hipLaunchKernelGGL(k_tile_sums<3>, dim3(1), dim3(256), 0, st, a.block_part, a.n_tiles,
                            a.result, a.seq);
     return (int)hipGetLastError();
 }
@@ -967,13 +871,9 @@ size_t edge_lds_bytes(int mode, int K, int C) { return EdgeLds(mode, K, C).total
 
 int launch_edge(hipStream_t st, int mode, const EdgeArgs &a, hipEvent_t after_edge) {
     const size_t lds = edge_lds_bytes(mode, a.K, a.C);
-    if (lds > kCuLdsBytes) return (int)hipErrorInvalidValue;
-    switch (a.K) {
-        case 2: return launch_edge_k<2>(st, mode, a, lds, after_edge);
-        case 4: return launch_edge_k<4>(st, mode, a, lds, after_edge);
-        case 20: return launch_edge_k<20>(st, mode, a, lds, after_edge);
-        default: return (int)hipErrorInvalidValue;
-    }
+    if (lds > kCuLdsBytes || !known_k(a.K)) return (int)hipErrorInvalidValue;
+    return dispatch_k(a.K,
+                      [&](auto k) { return launch_edge_k<k()>(st, mode, a, lds, after_edge); });
 }
 
 template <int TPW>
@@ -1015,12 +915,8 @@ int launch_ascbias(hipStream_t st, const AscArgs &a) {
     if (a.C > 64) return (int)hipErrorInvalidValue;
     int64_t nb = (a.first + 255) / 256;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, 1024))), block(256);
-    switch (a.K) {
-        case 2: hipLaunchKernelGGL(k_ascbias<2>, grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(k_ascbias<4>, grid, block, 0, st, a); break;
-        case 20: hipLaunchKernelGGL(k_ascbias<20>, grid, block, 0, st, a); break;
-        default: return (int)hipErrorInvalidValue;
-    }
+    if (!known_k(a.K)) return (int)hipErrorInvalidValue;
+    dispatch_k(a.K, [&](auto k) { hipLaunchKernelGGL(k_ascbias<k()>, grid, block, 0, st, a); });
     return (int)hipGetLastError();
 }
 

@@ -24,8 +24,9 @@
 //
 // Mapping (k_edge's): a workgroup is one 64-site tile, a lane a site, wave w owns
 // rate categories w, w + nw, ...; the categories of a site meet in LDS, where wave k mixes
-// arrangement k exactly as k_edge mixes its edge.  Every workgroup writes its 9 sums; a
-// one-workgroup second launch adds them in a fixed order (k_edge_sum's), bitwise repeatable.
+// arrangement k exactly as k_edge mixes its edge (mix_derivs).  Every workgroup writes its 9
+// sums; a one-workgroup second launch adds them in a fixed order (k_tile_sums), bitwise
+// repeatable.
 #include <math.h>
 
 #include <algorithm>
@@ -57,18 +58,13 @@ __host__ __device__ inline int quartet_waves(int K, int C) {
     return C < quartet_max_waves(K) ? C : quartet_max_waves(K);
 }
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][pendant
-// exponentials 4*C*K][central exponentials and their two derivative factors 3*3*C*K]
-// [per-(arrangement, category, site) f, f', f'', log scaler: 3*4*C*64]
-struct QuartetLds {
-    size_t evecs, ivecs, evals, pi, rates, ex, eg, vals, total;
-    __host__ __device__ QuartetLds(int K, int C) {
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        pi = evals + K;
-        rates = pi + K;
-        ex = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+// LDS of one workgroup (doubles): the model (ModelLds), then [pendant exponentials 4*C*K]
+// [central exponentials and their two derivative factors 3*3*C*K][per-(arrangement, category,
+// site) f, f', f'', log scaler: 3*4*C*64]
+struct QuartetLds : ModelLds {
+    size_t ex, eg, vals, total;
+    __host__ __device__ QuartetLds(int K, int C) : ModelLds(K, C) {
+        ex = body;
         eg = ex + (size_t)4 * C * K;
         vals = eg + (size_t)9 * C * K;
         total = vals + (size_t)12 * C * kLanes;
@@ -95,30 +91,18 @@ __global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs 
                  *pi = lds + L.pi, *rt = lds + L.rates, *ex = lds + L.ex, *eg = lds + L.eg;
     double *vals = lds + L.vals;
 
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-        lds[L.evecs + i] = a.evecs[i];
-        lds[L.ivecs + i] = a.ivecs[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        lds[L.evals + i] = a.evals[i];
-        lds[L.pi + i] = a.pi[i];
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    load_model<K>(a, lds, L);
     __syncthreads();
-    // e^{lambda (l r)} of the four pendant edges, build_p's arithmetic: [node][category][state]
-    for (int idx = threadIdx.x; idx < 4 * C * K; idx += blockDim.x) {
-        const int j = idx % K, ic = idx / K, c = ic % C, i = ic / C;
-        lds[L.ex + idx] = exp(el[j] * (q.l[i] * rt[c]));
-    }
+    // e^{lambda (l r)} of the four pendant edges: [node][category][state]
+    exp_tables<K>(lds + L.ex, el, rt, C, 4, q.l);
     // central edge of arrangement k: e, (lambda r) e, (lambda r)^2 e at [k][order][category][state]
     for (int idx = threadIdx.x; idx < 3 * C * K; idx += blockDim.x) {
         const int j = idx % K, kc = idx / K, c = kc % C, k = kc / C;
-        const double r = rt[c], x = el[j] * r;
-        const double e = exp(el[j] * (q.t[k] * r));
+        const double lam = el[j], r = rt[c], e = exp_lrt(lam, r, q.t[k]);
         double *g = lds + L.eg + (size_t)3 * k * C * K + (size_t)c * K + j;
         g[0] = e;
-        g[(size_t)C * K] = x * e;
-        g[(size_t)2 * C * K] = (x * x) * e;
+        g[(size_t)C * K] = exp_lrt_d(e, lam, r, 1);
+        g[(size_t)2 * C * K] = exp_lrt_d(e, lam, r, 2);
     }
     __syncthreads();
 
@@ -183,34 +167,13 @@ __global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs 
         }
     }
     __syncthreads();
-    // wave k mixes the categories of arrangement k: k_edge's EDGE_DERIV mix, value for value
+    // wave k mixes the categories of arrangement k
     for (int k = w; k < 3; k += nw) {
-        const double *vk = vals + (size_t)4 * k * C * kLanes + l;
         double v0 = 0.0, v1 = 0.0, v2 = 0.0;
         if (site < a.S) {
-            const double pw = a.pattern_w[site];
-            double smax = -INFINITY;
-            for (int c = 0; c < C; ++c)
-                if (vk[c * kLanes] > 0.0) smax = fmax(smax, vk[(3 * C + c) * kLanes]);
-            double Ls = 0.0, N1 = 0.0, N2 = 0.0;
-            for (int c = 0; c < C; ++c) {
-                if (!(vk[c * kLanes] > 0.0)) continue;
-                const double sc = vk[(3 * C + c) * kLanes];
-                const double we = a.weights[c] * (sc == smax ? 1.0 : exp(sc - smax));
-                Ls += we * vk[c * kLanes];
-                N1 += we * vk[(C + c) * kLanes];
-                N2 += we * vk[(2 * C + c) * kLanes];
-            }
-            if (Ls > 0.0) {
-                const double d1 = N1 / Ls;
-                v0 = pw * (smax + log(Ls));
-                v1 = pw * d1;
-                v2 = pw * (N2 / Ls - d1 * d1);
-            } else if (pw != 0.0) {
-                v0 = -INFINITY;  // every category has f <= 0 (lnl_node's -inf)
-            }
-            if constexpr (SITES)
-                q.site[(int64_t)k * q.site_ld + site] = Ls > 0.0 ? smax + log(Ls) : -INFINITY;
+            const double sl = mix_derivs(vals + (size_t)4 * k * C * kLanes + l, C, a.weights,
+                                         a.pattern_w[site], v0, v1, v2);
+            if constexpr (SITES) q.site[(int64_t)k * q.site_ld + site] = sl;
         }
         v0 = wave_sum(v0);
         v1 = wave_sum(v1);
@@ -224,39 +187,10 @@ __global__ void __launch_bounds__(64 * quartet_max_waves(K)) k_quartet(EdgeArgs 
     }
 }
 
-// second launch: the 9 sums over the workgroups' partials in a fixed order (k_edge_sum's:
-// partial b by thread b % 256, a 64-lane tree, the four waves in order)
-__global__ void __launch_bounds__(256) k_quartet_sum(const double *__restrict__ part, int n,
-                                                     double *__restrict__ result) {
-    __shared__ double red[9 * 4];
-    double s[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s[k] = 0.0;
-    for (int b = threadIdx.x; b < n; b += blockDim.x)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) s[k] += part[9 * (size_t)b + k];
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        s[k] = wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) red[9 * w + k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-        double r = 0.0;
-        for (int k = 0; k < 4; ++k) r += red[9 * k + threadIdx.x];
-        result[threadIdx.x] = r;
-    }
-}
-
 size_t quartet_lds_bytes(int K, int C) { return QuartetLds(K, C).total * sizeof(double); }
 
 // the largest C whose tables and mix area fit the LDS of a CU (K = 2: 25, 4: 24, 20: 19)
-int quartet_max_cat(int K) {
-    int C = 0;
-    while (quartet_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
-    return C;
-}
+int quartet_max_cat(int K) { return max_cat(K, quartet_lds_bytes, INT_MAX); }
 
 int node_is_tip(const pu_ctx *c, int node) { return c->tip_slot[node] >= 0; }
 
@@ -299,16 +233,12 @@ int quartet_eval(pu_ctx *c, const NodeSrc *x, const double *l, const double *t, 
     q.site_ld = site_ld;
     int rc;
     if ((rc = c->q_timer.begin(c))) return rc;
-    switch (c->K) {
-        case 2: launch_quartet_k<2>(c->stream, a, q); break;
-        case 4: launch_quartet_k<4>(c->stream, a, q); break;
-        default: launch_quartet_k<20>(c->stream, a, q); break;
-    }
+    dispatch_k(c->K, [&](auto k) { launch_quartet_k<k()>(c->stream, a, q); });
     HIPCHK(&c->err, hipGetLastError());
     if ((rc = c->q_timer.end(c))) return rc;
     if (!out9) return c->q_timer.stamp(c);
-    hipLaunchKernelGGL(k_quartet_sum, dim3(1), dim3(256), 0, c->stream, c->d_q_part, c->n_tiles,
-                       c->d_q_res_host);
+    hipLaunchKernelGGL(k_tile_sums<9>, dim3(1), dim3(256), 0, c->stream, c->d_q_part, c->n_tiles,
+                       c->d_q_res_host, 0.0);
     HIPCHK(&c->err, hipGetLastError());
     HIPCHK(&c->err, hipStreamSynchronize(c->stream));
     if ((rc = c->q_timer.stamp(c))) return rc;
@@ -368,9 +298,7 @@ int sweep_walk(pu_ctx *c, const char *fn, int n_rows, const int32_t *rows, doubl
 extern "C" {
 
 int pu_quartet_max_cat(int n_states) {
-    if (n_states != 2 && n_states != 4 && n_states != 20)
-        return set_err(nullptr, PU_E_ARG, "pu_quartet_max_cat: K=%d is not supported", n_states);
-    return quartet_max_cat(n_states);
+    return max_cat_call("pu_quartet_max_cat", n_states, quartet_max_cat);
 }
 
 int pu_quartet_derivs(pu_ctx *c, const int32_t *nodes, const double *lens, const double *t,

@@ -27,12 +27,13 @@
 // W_pc(k) = w_c e^{sigma_pc - m_p} T_pc(k) as [p][c][k], m_p and -- for a pendant length l0 --
 // the log table G[p][code] = m_p + log sum_c sum_k W_pc(k) e^{lambda_k r_c l0} u_k(code).
 // k_place_prescore adds sw_s G[p(s)][code_qs] over fixed chunks of kPlaceChunk sites, one
-// workgroup per (query, chunk), and k_place_chunk_sum adds a query's chunks in ascending order.
+// workgroup per (query, chunk), and k_row_sums adds a query's chunks in ascending order.
 // k_place_newton runs the Newton rule (pu_newton.h) for one query per workgroup on W.  Every sum runs
 // in a fixed order and nothing written is read by another workgroup of the same launch: two
 // runs are bitwise equal, and a query's numbers do not depend on the other queries.
 #include <math.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -50,7 +51,7 @@ namespace {
 constexpr int kPlaceMaxWaves = 8;  // k_place_table
 constexpr int kPlaceChunk = 2048;  // sites per k_place_prescore workgroup: a constant, so that a
                                    // query's sum order depends on nothing else
-constexpr int kPlaceThreads = 256;  // k_place_prescore, k_place_chunk_sum
+constexpr int kPlaceThreads = 256;  // k_place_prescore
 // k_place_newton: 16 waves on one candidate.  A walk over many edges launches few candidates per
 // edge, each workgroup alone on its CU and bound by the latency of its strided reads of W: the
 // refine pass of 5000 candidates over 97 edges (cfg2) took 770 ms with 4 waves
@@ -72,18 +73,13 @@ struct TableArgs {
     double *G;        // [S][n_codes] (nullptr: not written)
 };
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][u 32*K]
-// [e^{lambda r t/2} C*K][e^{lambda r l0} C*K][P C*K*K][m 64][per (category, pattern): a / T / W
-// (0..K-1), sum_i a, sigma -- later the mix weight: C*(K+2)*64]
-struct PlaceLds {
-    size_t evecs, ivecs, evals, pi, rates, u, ex, ex0, P, mx, vals, total;
-    __host__ __device__ PlaceLds(int K, int C) {
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        pi = evals + K;
-        rates = pi + K;
-        u = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+// LDS of one workgroup (doubles): the model (ModelLds), then [u 32*K][e^{lambda r t/2} C*K]
+// [e^{lambda r l0} C*K][P C*K*K][m 64][per (category, pattern): a / T / W (0..K-1), sum_i a,
+// sigma -- later the mix weight: C*(K+2)*64]
+struct PlaceLds : ModelLds {
+    size_t u, ex, ex0, P, mx, vals, total;
+    __host__ __device__ PlaceLds(int K, int C) : ModelLds(K, C) {
+        u = body;
         ex = u + (size_t)kMaxCodes * K;
         ex0 = ex + (size_t)C * K;
         P = ex0 + (size_t)C * K;
@@ -109,33 +105,13 @@ __global__ void __launch_bounds__(64 * kPlaceMaxWaves) k_place_table(EdgeArgs a,
     double *vals = lds + L.vals, *mx = lds + L.mx;
     constexpr int kRow = (K + 2) * kLanes;  // doubles per category in vals
 
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-        lds[L.evecs + i] = a.evecs[i];
-        lds[L.ivecs + i] = a.ivecs[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        lds[L.evals + i] = a.evals[i];
-        lds[L.pi + i] = a.pi[i];
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    load_model<K>(a, lds, L);
     for (int i = threadIdx.x; i < q.n_codes * K; i += blockDim.x) lds[L.u + i] = q.u[i];
     __syncthreads();
-    // P_c(t/2) = evecs diag(e^{lambda (t/2 r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
-    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
-        const int k = idx % K, c = idx / K;
-        lds[L.ex + idx] = exp(el[k] * (q.half * rt[c]));
-        lds[L.ex0 + idx] = exp(el[k] * (q.l0 * rt[c]));
-    }
+    const double t2[2] = {q.half, q.l0};  // ex, ex0: adjacent tables
+    exp_tables<K>(lds + L.ex, el, rt, C, 2, t2);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
-        const int ij = idx % (K * K), c = idx / (K * K);
-        const int i = ij / K, j = ij - i * K;
-        const double *e = ex + c * K;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-        lds[L.P + idx] = acc;
-    }
+    p_tables<K, false>(lds + L.P, ev, iv, ex, rt, C);  // P_c(t/2)
     __syncthreads();
 
     // K = 20: the state loops stay rolled over the rows (k_ancestral's way: the rows of P and V
@@ -177,22 +153,11 @@ __global__ void __launch_bounds__(64 * kPlaceMaxWaves) k_place_table(EdgeArgs a,
     }
     __syncthreads();
     if (w == 0) {
-        // wave 0 mixes the categories of its 64 patterns.  Only categories with sum_i a > 0
-        // take part (k_edge's rule: an all-zero vector keeps an unrescaled scaler, which must
-        // not set m); the mix weight w_c e^{sigma_c - m} replaces sigma_c
+        // wave 0 mixes the categories of its 64 patterns on sum_i a; the mix weight w_c
+        // e^{sigma_c - m} replaces sigma_c
         double *vs = vals + l;
-        double m = -INFINITY;
-        for (int c = 0; c < C; ++c)
-            if (vs[(size_t)c * kRow + K * kLanes] > 0.0)
-                m = fmax(m, vs[(size_t)c * kRow + (K + 1) * kLanes]);
-        for (int c = 0; c < C; ++c) {
-            double we = 0.0;
-            if (vs[(size_t)c * kRow + K * kLanes] > 0.0) {
-                const double sc = vs[(size_t)c * kRow + (K + 1) * kLanes];
-                we = a.weights[c] * (sc == m ? 1.0 : exp(sc - m));
-            }
-            vs[(size_t)c * kRow + (K + 1) * kLanes] = we;
-        }
+        const double m = mix_max(vs + K * kLanes, vs + (K + 1) * kLanes, kRow, C);
+        mix_weights(vs + K * kLanes, vs + (K + 1) * kLanes, kRow, C, a.weights, m);
         mx[l] = m;
         if (live) q.m[site] = m;
     }
@@ -276,17 +241,6 @@ __global__ void __launch_bounds__(kPlaceThreads) k_place_prescore(QueryDev d, in
         for (int k = 0; k < kPlaceThreads / 64; ++k) r += red[k];
         part[blk] = r;
     }
-}
-
-// second launch: a thread per query adds its chunks in ascending order
-__global__ void __launch_bounds__(kPlaceThreads) k_place_chunk_sum(const double *__restrict__ part,
-                                                                   int n_query, int n_chunks,
-                                                                   double *__restrict__ score) {
-    const int64_t qi = (int64_t)blockIdx.x * kPlaceThreads + threadIdx.x;
-    if (qi >= n_query) return;
-    double s = 0.0;
-    for (int k = 0; k < n_chunks; ++k) s += part[(size_t)qi * n_chunks + k];
-    score[qi] = s;
 }
 
 struct NewtonArgsP {
@@ -397,10 +351,7 @@ size_t place_lds_bytes(int K, int C) { return PlaceLds(K, C).total * sizeof(doub
 
 // the largest C whose tables fit the LDS of a CU and a context can hold
 int place_max_cat(int K) {
-    int C = 0;
-    while (C < kCtxMaxCat && (C + 1) * K <= kPlaceMaxCK && place_lds_bytes(K, C + 1) <= kCuLdsBytes)
-        ++C;
-    return C;
+    return max_cat(K, place_lds_bytes, std::min(kCtxMaxCat, kPlaceMaxCK / K));
 }
 
 }  // namespace
@@ -540,11 +491,7 @@ int table_enqueue(pu_ctx *c, NodeSrc n, NodeSrc o, double t, const QueryHost &h,
     q.G = with_G ? s->d_G : nullptr;
     int rc;
     if ((rc = s->timer[0].begin(c))) return rc;
-    switch (c->K) {
-        case 2: launch_table_k<2>(c->stream, a, q); break;
-        case 4: launch_table_k<4>(c->stream, a, q); break;
-        default: launch_table_k<20>(c->stream, a, q); break;
-    }
+    dispatch_k(c->K, [&](auto k) { launch_table_k<k()>(c->stream, a, q); });
     HIPCHK(&c->err, hipGetLastError());
     return s->timer[0].end(c);
 }
@@ -562,10 +509,7 @@ int prescore_enqueue(pu_ctx *c, const QueryDev &d, int n_query, double *score_de
                        d, n_query, s->d_G, s->d_part);
     HIPCHK(&c->err, hipGetLastError());
     if ((rc = s->timer[1].end(c))) return rc;
-    hipLaunchKernelGGL(k_place_chunk_sum, dim3((unsigned)((n_query + kPlaceThreads - 1) /
-                                                          kPlaceThreads)),
-                       dim3(kPlaceThreads), 0, c->stream, s->d_part, n_query, d.n_chunks,
-                       score_dev);
+    launch_row_sums(c->stream, s->d_part, n_query, d.n_chunks, score_dev);
     HIPCHK(&c->err, hipGetLastError());
     return PU_OK;
 }
@@ -589,11 +533,9 @@ int newton_enqueue(pu_ctx *c, const QueryDev &d, const int32_t *list_dev, int n,
     int rc;
     if ((rc = s->timer[2].begin(c))) return rc;
     const dim3 grid((unsigned)n), block(kNewtonThreads);
-    switch (c->K) {
-        case 2: hipLaunchKernelGGL(k_place_newton<2>, grid, block, 0, c->stream, d, a); break;
-        case 4: hipLaunchKernelGGL(k_place_newton<4>, grid, block, 0, c->stream, d, a); break;
-        default: hipLaunchKernelGGL(k_place_newton<20>, grid, block, 0, c->stream, d, a); break;
-    }
+    dispatch_k(c->K, [&](auto k) {
+        hipLaunchKernelGGL(k_place_newton<k()>, grid, block, 0, c->stream, d, a);
+    });
     HIPCHK(&c->err, hipGetLastError());
     return s->timer[2].end(c);
 }
@@ -603,9 +545,7 @@ int newton_enqueue(pu_ctx *c, const QueryDev &d, const int32_t *list_dev, int n,
 extern "C" {
 
 int pu_place_max_cat(int n_states) {
-    if (n_states != 2 && n_states != 4 && n_states != 20)
-        return set_err(nullptr, PU_E_ARG, "pu_place_max_cat: K=%d is not supported", n_states);
-    return place_max_cat(n_states);
+    return max_cat_call("pu_place_max_cat", n_states, place_max_cat);
 }
 
 int pu_place_edge(pu_ctx *c, int node, int other, double length, int n_query, int64_t n_sites,

@@ -1,11 +1,16 @@
 // pu_resident.h -- the host layer that the calls on the device-resident partials of a context
 // share (pu_edge.cpp's optimising sweep, pu_nni.hip, pu_ancestral.hip, pu_counts.hip,
-// pu_place.hip): the limits their kernels are sized by, the one list of refusals, a context
-// buffer that only grows, and the walk over the rows of the optimising traversal.  The
+// pu_place.hip, pu_spr.hip): the limits their kernels are sized by and the category limit that
+// follows from them, the dispatch on the alphabet, the one list of refusals, a context buffer
+// that only grows, and the walk over the rows of the optimising traversal.  The
 // non-template bodies are in pu_edge.cpp, next to the edge functions they wrap; LaunchTimer, a
 // member of the context, is declared in pu_ctx.h.  A call's own temporaries are pu_service.h's
 // HostCall.  Not part of the public ABI: nothing declared here is exported by the library.
 #pragma once
+#include <limits.h>
+
+#include <type_traits>
+
 #include "pu_ctx.h"
 
 #pragma GCC visibility push(hidden)
@@ -27,6 +32,34 @@ int edge_update_ops(pu_ctx *c, int n, const int32_t *ops, const double *brlens);
 // header lists them: edge_prepare, kept partials, an eigen-decomposed model, no ascertainment
 // correction, K in {2, 4, 20} and at most max_cat categories (the kernel's *_max_cat(K))
 int resident_ready(pu_ctx *c, const char *what, int max_cat);
+
+// the alphabets the resident kernels are built for, and one of them as a template argument:
+// f(std::integral_constant<int, K>) for K in {2, 4, 20} (any other K, which resident_ready
+// refuses, goes to 20)
+inline bool known_k(int K) { return K == 2 || K == 4 || K == 20; }
+template <class F>
+auto dispatch_k(int K, F f) {
+    switch (K) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 20>{});
+    }
+}
+
+// a kernel's category limit: the largest C <= cap whose lds_bytes(K, C) fit the LDS of a CU
+template <class Bytes>
+int max_cat(int K, Bytes lds_bytes, int cap = kCtxMaxCat) {
+    int C = 0;
+    while (C < cap && lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
+    return C;
+}
+
+// the pu_*_max_cat entry points: PU_E_ARG for an alphabet without kernels
+template <class F>
+int max_cat_call(const char *fn, int K, F kernel_max_cat) {
+    if (!known_k(K)) return set_err(nullptr, PU_E_ARG, "%s: K=%d is not supported", fn, K);
+    return kernel_max_cat(K);
+}
 
 // a device buffer of the context that only grows: at least `need` elements in p
 template <class T>

@@ -23,7 +23,7 @@
 // k_regraft (k_ancestral's mapping: a workgroup is one 64-pattern tile, a lane a pattern, wave w
 // owns categories w, w + nw, ...) builds P_c(t/2) and P_c(l) in LDS, forms the three products
 // row by row and leaves g and sigma of its categories in LDS; wave 0 mixes them and writes the
-// tile's weighted sum with a fixed lane tree.  k_regraft_sum, one thread per scored row, adds a
+// tile's weighted sum with a fixed lane tree.  k_row_sums, one thread per scored row, adds a
 // row's tiles in ascending order.  Every sum runs in a fixed order and nothing written is read
 // by another workgroup of the same launch: a score is bitwise repeatable and depends only on
 // (A, B, S, t, l) and the pattern count.  The kernels only read the context's partials.
@@ -42,7 +42,6 @@ using namespace pu;
 namespace {
 
 constexpr int kSprMaxWaves = 8;  // k_regraft
-constexpr int kSprThreads = 256;  // k_regraft_sum
 
 __host__ __device__ inline int spr_waves(int C) { return C < kSprMaxWaves ? C : kSprMaxWaves; }
 
@@ -53,17 +52,12 @@ struct RegraftArgs {
     double *part;     // [n_tiles] the tiles' weighted sums of this row
 };
 
-// LDS of one workgroup (doubles): [evecs K*K][ivecs K*K][evals K][pi K][rates C][e^{lambda r t/2}
-// C*K][e^{lambda r l} C*K][P(t/2) C*K*K][P(l) C*K*K][per (category, pattern): g, sigma: C*2*64]
-struct SprLds {
-    size_t evecs, ivecs, evals, pi, rates, ex, exl, P, Pl, vals, total;
-    __host__ __device__ SprLds(int K, int C) {
-        evecs = 0;
-        ivecs = evecs + (size_t)K * K;
-        evals = ivecs + (size_t)K * K;
-        pi = evals + K;
-        rates = pi + K;
-        ex = (rates + C + 1) & ~size_t(1);  // 16-byte aligned tables
+// LDS of one workgroup (doubles): the model (ModelLds), then [e^{lambda r t/2} C*K][e^{lambda r
+// l} C*K][P(t/2) C*K*K][P(l) C*K*K][per (category, pattern): g, sigma: C*2*64]
+struct SprLds : ModelLds {
+    size_t ex, exl, P, Pl, vals, total;
+    __host__ __device__ SprLds(int K, int C) : ModelLds(K, C) {
+        ex = body;
         exl = ex + (size_t)C * K;
         P = exl + (size_t)C * K;
         Pl = P + (size_t)C * K * K;
@@ -86,35 +80,20 @@ __global__ void __launch_bounds__(64 * kSprMaxWaves) k_regraft(EdgeArgs a, Regra
                  *P = lds + L.P, *Pl = lds + L.Pl;
     double *vals = lds + L.vals;
 
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x) {
-        lds[L.evecs + i] = a.evecs[i];
-        lds[L.ivecs + i] = a.ivecs[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        lds[L.evals + i] = a.evals[i];
-        lds[L.pi + i] = a.pi[i];
-    }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) lds[L.rates + i] = a.rates[i];
+    load_model<K>(a, lds, L);
     __syncthreads();
-    // P_c(t) = evecs diag(e^{lambda (t r_c)}) ivecs, build_p's arithmetic (pu_edge.hip)
-    for (int idx = threadIdx.x; idx < C * K; idx += blockDim.x) {
-        const int k = idx % K, c = idx / K;
-        lds[L.ex + idx] = exp(el[k] * (q.half * rt[c]));
-        lds[L.exl + idx] = exp(el[k] * (q.l * rt[c]));
-    }
+    const double t2[2] = {q.half, q.l};  // ex, exl: adjacent tables
+    exp_tables<K>(lds + L.ex, el, rt, C, 2, t2);
     __syncthreads();
+    // p_tables<K, false> of both tables, a thread forming entry (i, j) of P_c(t/2) and of P_c(l)
+    // from one read of U and U^-1 (dealt one entry per turn, the K = 20 kernel took 6 % longer)
     for (int idx = threadIdx.x; idx < C * K * K; idx += blockDim.x) {
         const int ij = idx % (K * K), c = idx / (K * K);
         const int i = ij / K, j = ij - i * K;
-        const double *e = ex + c * K, *e2 = exl + c * K;
-        double acc = 0.0, acc2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            acc = fma(ev[i * K + k] * e[k], iv[k * K + j], acc);
-            acc2 = fma(ev[i * K + k] * e2[k], iv[k * K + j], acc2);
-        }
-        lds[L.P + idx] = acc;
-        lds[L.Pl + idx] = acc2;
+        const double p = p_entry<K>(ev, iv, ex + c * K, i, j);
+        const double pl = p_entry<K>(ev, iv, exl + c * K, i, j);
+        lds[L.P + idx] = p;
+        lds[L.Pl + idx] = pl;
     }
     __syncthreads();
 
@@ -145,49 +124,29 @@ __global__ void __launch_bounds__(64 * kSprMaxWaves) k_regraft(EdgeArgs a, Regra
     __syncthreads();
     if (w != 0) return;
 
-    // wave 0 mixes the categories of its 64 patterns.  Only categories with g > 0 take part
-    // (k_edge's rule: an all-zero vector keeps an unrescaled scaler, which must not set m)
+    // wave 0 mixes the categories of its 64 patterns on g
     double v0 = 0.0;
     if (site < a.S) {
         const double *vs = vals + l;
-        double m = -INFINITY;
-        for (int c = 0; c < C; ++c)
-            if (vs[(size_t)(2 * c) * kLanes] > 0.0) m = fmax(m, vs[(size_t)(2 * c + 1) * kLanes]);
+        const double m = mix_max(vs, vs + kLanes, 2 * kLanes, C);
         double Z = 0.0;
         for (int c = 0; c < C; ++c) {
             const double g = vs[(size_t)(2 * c) * kLanes];
-            if (g > 0.0) {
-                const double sc = vs[(size_t)(2 * c + 1) * kLanes];
-                Z += (a.weights[c] * (sc == m ? 1.0 : exp(sc - m))) * g;
-            }
+            if (mix_takes_part(g))
+                Z += mix_weight(a.weights[c], vs[(size_t)(2 * c + 1) * kLanes], m) * g;
         }
         const double pw = a.pattern_w[site];
-        if (pw != 0.0) v0 = Z > 0.0 ? pw * (m + log(Z)) : -INFINITY;
+        if (pw != 0.0) v0 = mix_lnl(pw, m, Z);  // (weight 0 adds +0, not 0 x lnL)
     }
     v0 = wave_sum(v0);
     if (l == 0) q.part[blockIdx.x] = v0;
-}
-
-// second launch: a thread per scored row adds the row's tiles in ascending order
-__global__ void __launch_bounds__(kSprThreads) k_regraft_sum(const double *__restrict__ part,
-                                                             int n_rows, int n_tiles,
-                                                             double *__restrict__ score) {
-    const int64_t r = (int64_t)blockIdx.x * kSprThreads + threadIdx.x;
-    if (r >= n_rows) return;
-    double s = 0.0;
-    for (int k = 0; k < n_tiles; ++k) s += part[(size_t)r * n_tiles + k];
-    score[r] = s;
 }
 
 size_t spr_lds_bytes(int K, int C) { return SprLds(K, C).total * sizeof(double); }
 
 // the largest C whose two sets of P matrices and mix area fit the LDS of a CU, and a context can
 // hold (K = 2: 64, 4: 64, 20: 20)
-int spr_max_cat(int K) {
-    int C = 0;
-    while (C < kCtxMaxCat && spr_lds_bytes(K, C + 1) <= kCuLdsBytes) ++C;
-    return C;
-}
+int spr_max_cat(int K) { return max_cat(K, spr_lds_bytes); }
 
 }  // namespace
 
@@ -242,19 +201,14 @@ int regraft_enqueue(pu_ctx *c, int na, int nb, int ns, double t, double l, size_
     q.l = l;
     q.part = s->d_part + k * (size_t)c->n_tiles;
     if ((rc = s->timer.begin(c))) return rc;
-    switch (c->K) {
-        case 2: launch_regraft_k<2>(c->stream, a, q); break;
-        case 4: launch_regraft_k<4>(c->stream, a, q); break;
-        default: launch_regraft_k<20>(c->stream, a, q); break;
-    }
+    dispatch_k(c->K, [&](auto k) { launch_regraft_k<k()>(c->stream, a, q); });
     HIPCHK(&c->err, hipGetLastError());
     return s->timer.end(c);
 }
 
 // the first n rows of the tile sums into score_dev[n]
 int sum_enqueue(pu_ctx *c, int n, double *score_dev) {
-    hipLaunchKernelGGL(k_regraft_sum, dim3((unsigned)((n + kSprThreads - 1) / kSprThreads)),
-                       dim3(kSprThreads), 0, c->stream, c->spr->d_part, n, c->n_tiles, score_dev);
+    launch_row_sums(c->stream, c->spr->d_part, n, c->n_tiles, score_dev);
     HIPCHK(&c->err, hipGetLastError());
     return PU_OK;
 }
@@ -279,9 +233,7 @@ int check_scored(pu_ctx *c, const char *fn, long long row, int na, int nb, int n
 extern "C" {
 
 int pu_regraft_max_cat(int n_states) {
-    if (n_states != 2 && n_states != 4 && n_states != 20)
-        return set_err(nullptr, PU_E_ARG, "pu_regraft_max_cat: K=%d is not supported", n_states);
-    return spr_max_cat(n_states);
+    return max_cat_call("pu_regraft_max_cat", n_states, spr_max_cat);
 }
 
 int pu_regraft_edge(pu_ctx *c, int a, int b, int s, double t, double l, double *score_out) {
