@@ -905,6 +905,41 @@ int pu_parsimony_stepwise(int device, int n_taxa, int64_t n_pat, int n_codes, in
                           const uint8_t *codes, const double *code_table, const int64_t *weights,
                           int n_rep, const int32_t *orders, int32_t *edges_out,
                           uint64_t *step_lengths_out, uint64_t *lengths_out);
+/* ---- Parsimony SPR (normative; tests/parsimony_spr_reference.py restates it) ----
+ * A tree is an edge list edges [2 n_taxa - 3][2] in DESIGN 4.22's form, as pu_parsimony_stepwise
+ * returns it: tips 0 .. n_taxa - 1, internal nodes n_taxa .. 2 n_taxa - 3, each on exactly
+ * three edges.  Prune direction d = 2 e + side prunes the subtree on s's side of edge e, (s, u) =
+ * edges[e] for side 0 and reversed for side 1; it is valid iff u is internal.  u's other two
+ * edges are ea < eb with far ends a, b; the rest tree T' has the merged edge (a, b) under id ea.
+ * Every other edge f of T' is a target, named by its id, at dist(f) = 1 next to the merged edge
+ * and one more per edge further away; radius = 0 is no limit, else only dist(f) <= radius.
+ *   score[d][f] = L(T) - miss(ea) + miss(f),  miss(g) = sum_p w[p] [D(s->u)(p) & E'(g)(p) = 0]
+ * is the exact length of the tree after the move (E'(g): the edge set of g in T', derived from
+ * the directional sets of T by a walk outward from the merged edge); every entry that is not a
+ * (valid direction, target) pair holds UINT64_MAX.  Applying (d, f), (x, y) = edges[f]:
+ * edges[ea] = (a, b), edges[f] = (x, u), edges[eb] = (u, y); edges[e] and all node ids stay.
+ * PU_E_ARG: everything pu_fitch_lengths refuses, an edge list that is not a binary tree over
+ * the rows, radius < 0, max_rounds < 0.  n_taxa = 3 is valid and has no move.
+ * Workspace and scores obey the 256 MiB rule above, chunked over trees, then directions, then
+ * patterns (PU_PARS_CHUNK, PU_PARS_WS); PU_PARS_LDS=bytes lowers the LDS the walk's arriving
+ * sets may use before they go to the workspace.  No result depends on any of them. */
+/* lengths_out [n_trees] = L(T); scores_out [n_trees][2 (2 n_taxa - 3)][2 n_taxa - 3]. */
+int pu_fitch_spr_scores(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                        const uint8_t *codes, const double *code_table, const int64_t *weights,
+                        int n_trees, const int32_t *edges, int radius, uint64_t *lengths_out,
+                        uint64_t *scores_out);
+/* The search, per tree: score the tree; best = the smallest score, ties to the lowest d, then
+ * the lowest f; stop if there is no target or best >= L; else apply the move, L = best, count a
+ * round; stop after max_rounds rounds (0: no limit).  edges_inout [n_trees][2 n_taxa - 3][2]
+ * (unchanged when the call fails), lengths_out [n_trees] the final lengths, rounds_out
+ * [n_trees]; moves_out, nullable, [n_trees][max_rounds][3] = (d, f, length after), rows past a
+ * tree's rounds zero -- refused when non-NULL with max_rounds = 0.  The host drives the
+ * rounds: one scoring pass per round for all unconverged trees, three numbers read back per
+ * tree and direction chunk (k_spr_argmin), the move applied on the host. */
+int pu_parsimony_spr(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                     const uint8_t *codes, const double *code_table, const int64_t *weights,
+                     int n_trees, int32_t *edges_inout, int radius, int max_rounds,
+                     uint64_t *lengths_out, int32_t *rounds_out, uint64_t *moves_out);
 /* Event timing (scripts/time_parsimony.py): with pu_parsimony_profile(device, 1) every call
  * above records events around its launches; pu_parsimony_kernel_ms returns the last call's
  * kernel time in ms, summed over its chunks and steps. */

@@ -175,6 +175,10 @@ SIGNATURES = {
                                          _P, _c_int, _P, _P]),
     "pu_parsimony_stepwise": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _c_int,
                                        _P, _P, _P, _P]),
+    "pu_fitch_spr_scores": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _c_int,
+                                     _P, _c_int, _P, _P]),
+    "pu_parsimony_spr": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _c_int, _P,
+                                  _c_int, _c_int, _P, _P, _P]),
     "pu_parsimony_profile": (_c_int, [_c_int, _c_int]),
     "pu_parsimony_kernel_ms": (_c_int, [_c_int, _P]),
     "pu_ctx_stream": (_P, [_P]),

@@ -1,5 +1,6 @@
 """Fitch parsimony on the GPU: tree lengths, exact insertion lengths and randomised
-stepwise-addition trees.
+stepwise-addition trees; and parsimony SPR: the exact lengths of all SPR neighbours
+of a tree given as an edge list, and the search on them.
 
 The reference has no parsimony; the rule is DESIGN 4.22's: state sets are the states a tip's code
 allows, ``c(A, B)`` is the intersection where it is non-empty and the union otherwise, and a
@@ -204,6 +205,99 @@ def stepwise_addition(coded_alignment, orders=None, n_rep=1, seed=0, weights=Non
                                           N.ptr(orders), N.ptr(edges), N.ptr(steps),
                                           N.ptr(lengths)), None, "pu_parsimony_stepwise")
     return edges, steps, lengths
+
+
+SENTINEL = np.uint64(0xFFFFFFFFFFFFFFFF)  # a score entry that is no (valid direction, target) pair
+
+
+def _edge_batch(edges, n):
+    """(int32 [T][2n-3][2], whether `edges` was one edge list)."""
+    e = np.ascontiguousarray(edges, dtype=np.int32)
+    single = e.ndim == 2
+    if single:
+        e = e[None]
+    if e.ndim != 3 or e.shape[1:] != (max(2 * n - 3, 0), 2) or e.shape[0] < 1:
+        raise ValueError("edges must be [2n-3][2] or [T][2n-3][2] with n = %d, not %r"
+                         % (n, np.shape(edges)))
+    return np.ascontiguousarray(e), single
+
+
+def spr_scores(coded_alignment, edges, weights=None, radius=None, device=0):
+    """pu_fitch_spr_scores: the exact parsimony length of every SPR neighbour of
+    the tree `edges` (int32 [2n-3][2] in DESIGN 4.22's form, or a batch [T][2n-3][2]).  Returns
+    (length, scores): L(T) (a Python int, or uint64 [T]) and uint64 [2(2n-3)][2n-3] (or
+    [T][...]), ``scores[d][f]`` the length after pruning direction ``d = 2e + side`` and
+    regrafting on edge f, ``SENTINEL`` where that is no move.  `radius` None or 0: no limit."""
+    codes, table, names = _alignment(coded_alignment)
+    n, n_pat = codes.shape
+    e, single = _edge_batch(edges, n)
+    w = integer_weights(weights, n_pat)
+    T, E = e.shape[0], e.shape[1]
+    lengths = np.zeros(T, dtype=np.uint64)
+    scores = np.zeros((T, 2 * E, E), dtype=np.uint64)
+    N.check(N.lib().pu_fitch_spr_scores(int(device), n, n_pat, table.shape[0], table.shape[1],
+                                        N.ptr(codes), N.ptr(table), N.ptr(w), T, N.ptr(e),
+                                        int(radius or 0), N.ptr(lengths), N.ptr(scores)), None,
+            "pu_fitch_spr_scores")
+    return (int(lengths[0]), scores[0]) if single else (lengths, scores)
+
+
+def spr_search(coded_alignment, edges, weights=None, radius=None, max_rounds=0,
+               return_moves=False, device=0):
+    """pu_parsimony_spr: per tree of `edges` (one edge list or a batch), rounds of
+    "score all SPR neighbours, take the shortest (ties: the lowest direction, then the lowest
+    edge) if it is shorter than the tree" until none is, or `max_rounds` rounds (0: no limit).
+    Returns (edges, length, rounds) -- for a batch int32 [T][2n-3][2], uint64 [T], int32 [T] --
+    and with `return_moves` (needs ``max_rounds > 0``) also the moves, uint64 [rounds][3] =
+    (d, f, length after) per tree."""
+    codes, table, names = _alignment(coded_alignment)
+    n, n_pat = codes.shape
+    e, single = _edge_batch(edges, n)
+    e = e.copy()
+    w = integer_weights(weights, n_pat)
+    max_rounds = int(max_rounds)
+    if return_moves and max_rounds <= 0:
+        raise ValueError("return_moves needs max_rounds > 0")
+    T = e.shape[0]
+    lengths = np.zeros(T, dtype=np.uint64)
+    rounds = np.zeros(T, dtype=np.int32)
+    moves = np.zeros((T, max_rounds, 3), dtype=np.uint64) if return_moves else None
+    N.check(N.lib().pu_parsimony_spr(int(device), n, n_pat, table.shape[0], table.shape[1],
+                                     N.ptr(codes), N.ptr(table), N.ptr(w), T, N.ptr(e),
+                                     int(radius or 0), max_rounds, N.ptr(lengths), N.ptr(rounds),
+                                     N.ptr(moves)), None, "pu_parsimony_spr")
+    out = [e[0], int(lengths[0]), int(rounds[0])] if single else [e, lengths, rounds]
+    if return_moves:
+        per_tree = [moves[t, :int(rounds[t])] for t in range(T)]
+        out.append(per_tree[0] if single else per_tree)
+    return tuple(out)
+
+
+def apply_spr_edges(edges, d, f):
+    """The edge list after the SPR move (d, f) of DESIGN 4.26, on the host: with ``(s, u)`` the
+    ends of edge ``d // 2`` (reversed for an odd d), ``ea < eb`` u's other two edges and a, b
+    their far ends, and ``(x, y) = edges[f]``: ``edges[ea] = (a, b)``, ``edges[f] = (x, u)``,
+    ``edges[eb] = (u, y)``.  A direction whose u is a tip, and an f that is no target's id
+    (edge d // 2, ea, eb, or an edge of the pruned subtree -- the last is not checked), are
+    refused."""
+    out = np.array(edges, dtype=np.int32).reshape(-1, 2)
+    n = (len(out) + 3) // 2
+    d, f = int(d), int(f)
+    e, side = d >> 1, d & 1
+    if not (0 <= e < len(out) and 0 <= f < len(out)):
+        raise ValueError("move (%d, %d) of %d edges" % (d, f, len(out)))
+    u = int(out[e, 1 - side])
+    if u < n:
+        raise ValueError("direction %d prunes towards tip %d" % (d, u))
+    (ea, a), (eb, b) = sorted((g, int(out[g, 0] if out[g, 1] == u else out[g, 1]))
+                              for g in np.flatnonzero((out == u).any(axis=1)) if g != e)
+    if f in (e, ea, eb):
+        raise ValueError("edge %d is no target of direction %d" % (f, d))
+    x, y = out[f]
+    out[ea] = (a, b)
+    out[f] = (x, u)
+    out[eb] = (u, y)
+    return out
 
 
 def edges_to_tree(edges, names, lengths=None):

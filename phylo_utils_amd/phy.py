@@ -37,7 +37,10 @@ replicates (``phylo_utils_amd.bootstrap``);
 parsimony (``phylo_utils_amd.parsimony``, the seed of ``--seed``; the reference has no tree
 builder), written to ``-o`` when given; one extra line ``parsimony = <length>`` comes before the
 ``lnL = `` line, and ``--nni``, ``--spr``, ``--optimise``, ``--support`` and ``-o`` follow as they do
-after ``--nj``.  ``--parsimony-score`` (after ``-t`` or ``--nj``) prints the same line for that tree
+after ``--nj``.  With ``--parsimony-spr [ROUNDS]`` (and ``--parsimony-radius R``), valid only with
+``--parsimony``, all R trees are refined by parsimony SPR before the shortest is kept
+(``parsimony.spr_search``: at most ROUNDS rounds each, default until no move shortens the tree) and
+the ``parsimony = `` line is the refined length.  ``--parsimony-score`` (after ``-t`` or ``--nj``) prints the same line for that tree
 and changes nothing else;
 ``--nni [ROUNDS]`` (after ``-t`` or ``--nj``) improves the topology by nearest-neighbour
 interchanges on the GPU before the ``lnL = `` line (``phylo_utils_amd.nni``, at most ROUNDS
@@ -204,6 +207,16 @@ def parse_cli(argv=None):
                     help="take the tree from randomised stepwise addition under Fitch parsimony, "
                          "the shortest of R addition orders (default 1; seed: --seed; no -t, no "
                          "--nj); prints a 'parsimony = ' line; -o receives its Newick")
+    ap.add_argument("--parsimony-spr", type=int, nargs="?", const=0, default=None,
+                    dest="parsimony_spr", metavar="ROUNDS",
+                    help="with --parsimony: refine all R stepwise-addition trees by parsimony "
+                         "SPR before the shortest is kept, at most ROUNDS rounds each (default "
+                         "0: until no move shortens the tree); the 'parsimony = ' line is the "
+                         "refined length")
+    ap.add_argument("--parsimony-radius", type=int, default=None, dest="parsimony_radius",
+                    metavar="R",
+                    help="with --parsimony-spr: regraft at most R edges away from where the "
+                         "subtree was pruned (default: no limit)")
     ap.add_argument("--parsimony-score", action="store_true", dest="parsimony_score",
                     help="after -t or --nj: print the tree's Fitch parsimony length as a "
                          "'parsimony = ' line before the lnL line")
@@ -263,6 +276,16 @@ def parse_cli(argv=None):
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "parsimony_spr", None) is not None:
+        if getattr(args, "parsimony", None) is None:
+            raise ValueError("--parsimony-spr needs --parsimony")
+        if args.parsimony_spr < 0:
+            raise ValueError("--parsimony-spr needs a number of rounds >= 0")
+    if getattr(args, "parsimony_radius", None) is not None:
+        if getattr(args, "parsimony_spr", None) is None:
+            raise ValueError("--parsimony-radius needs --parsimony-spr")
+        if args.parsimony_radius < 0:
+            raise ValueError("--parsimony-radius needs a radius >= 0")
     if getattr(args, "ancestral", None) is not None or getattr(args, "site_rates", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--ancestral and --site-rates exclude --simulate and --distances")
@@ -410,7 +433,9 @@ def run(args, out=None):
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
     if pars is not None:  # --parsimony: the shortest of R stepwise-addition trees
-        tree, pars_length, _ = tm.set_parsimony_tree(n_rep=pars, seed=args.seed)
+        tree, pars_length, _ = tm.set_parsimony_tree(
+            n_rep=pars, seed=args.seed, spr_rounds=getattr(args, "parsimony_spr", None),
+            spr_radius=getattr(args, "parsimony_radius", None))
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")

@@ -775,19 +775,26 @@ class TreeModel(object):
                                        weights=self.siteweights, per_pattern=per_pattern,
                                        device=self.device)
 
-    def set_parsimony_tree(self, n_rep=1, seed=0, min_length=1e-8):
+    def set_parsimony_tree(self, n_rep=1, seed=0, min_length=1e-8, spr_rounds=None,
+                           spr_radius=None):
         """A starting tree by randomised stepwise addition under Fitch parsimony
         (``parsimony.stepwise_addition``): `n_rep` random addition orders
         (``parsimony.random_orders(n, n_rep, seed)``), the shortest tree kept, ties to the lowest
-        replicate.  Every branch length is ``max(edge change count / sum of siteweights,
-        min_length)``.  Needs coded tips and no model at all, so it also serves the
-        non-reversible models ``set_nj_tree`` refuses.  Calls ``set_tree``; returns (tree,
+        replicate.  With `spr_rounds` a number, all `n_rep` trees are first refined in one batch
+        by parsimony SPR (``parsimony.spr_search``, DESIGN 4.26: at most `spr_rounds` rounds, 0
+        until no move improves, regrafts within `spr_radius` edges, None or 0 for no limit) and
+        the shortest refined tree is kept.  Every branch length is ``max(edge change count / sum
+        of siteweights, min_length)``.  Needs coded tips and no model at all, so it also serves
+        the non-reversible models ``set_nj_tree`` refuses.  Calls ``set_tree``; returns (tree,
         length, the lengths of all replicates)."""
         from . import parsimony
         aln = self._coded_alignment()
         w = parsimony.integer_weights(self.siteweights, aln[0].shape[1])
         edges, _, lengths = parsimony.stepwise_addition(aln, n_rep=n_rep, seed=seed, weights=w,
                                                         device=self.device)
+        if spr_rounds is not None:
+            edges, lengths, _ = parsimony.spr_search(aln, edges, weights=w, radius=spr_radius,
+                                                     max_rounds=spr_rounds, device=self.device)
         best = int(np.argmin(lengths))  # the first of equal lengths
         tree = parsimony.edges_to_tree(edges[best], aln[2])
         _, per_edge = parsimony.fitch_lengths(aln, tree, weights=w, per_edge=True,
