@@ -946,6 +946,54 @@ int pu_parsimony_spr(int device, int n_taxa, int64_t n_pat, int n_codes, int n_s
 int pu_parsimony_profile(int device, int on);
 int pu_parsimony_kernel_ms(int device, double *ms);
 
+/* ---- Sets of trees: splits, RF matrix, split counts (normative;
+ * tests/treeset_reference.py restates it) ----
+ * T = n_trees binary trees over the same n tips, tips 0 .. n - 1, internal nodes n .. 2n - 3.
+ * Each tree's 2n - 3 edges are numbered in the form's own edge order (below).  The split of an
+ * edge is the set of tips on the side of the edge that does not hold tip 0: a bitset of
+ * nw = ceil(n / 64) words, tip i at bit i & 63 of word i >> 6.  A split of 1 or n - 1 tips (a
+ * pendant edge) is trivial and has no id; every binary tree has exactly n - 3 others, one per
+ * internal edge.  The split table U holds the distinct non-trivial splits of all T trees in
+ * ascending order as unsigned integers of 64 nw bits, word nw - 1 the most significant; the id
+ * of a split is its index in U, and count[u] is the number of trees that hold split u (a tree
+ * holds a split at most once).  Two splits are equal only if all nw words are equal: no hash
+ * decides equality or order.  RF(a, b) = 2 (n - 3) - 2 |ids(a) & ids(b)|.  n = 3 is valid: no
+ * split, U = 0, every RF 0.
+ * form selects the encoding of `trees`:
+ *   PU_TREES_OPS    ops [T][n-2][3] = (parent, left, right) and roots [T][2], pu_fitch_lengths'
+ *                   form; edges 2 i = (left_i, parent_i), 2 i + 1 = (right_i, parent_i), then the
+ *                   root edge.
+ *   PU_TREES_JOINS  joins [T][n-2][2] and roots [T][2], pu_nj's form: op m is
+ *                   (n + m, joins[m][0], joins[m][1]); the edge order is the ops form's.
+ *   PU_TREES_EDGES  edges [T][2n-3][2], roots NULL, pu_parsimony_stepwise's form; the edge order
+ *                   is the list's own.
+ * Outputs: edge_ids_out [T][2n-3], the split id per edge, -1 on a pendant edge; n_unique_out
+ * [1] = U; uniq_bits_out (nullable) with room for T (n - 3) rows of nw words, the first U
+ * written; uniq_count_out (nullable) with room for T (n - 3), the first U written; rf_out
+ * (nullable) [n_rows][T], trees 0 .. n_rows - 1 against all.  A nullable output that is NULL
+ * changes no other.
+ * PU_E_ARG, before any device is touched: a null trees, edge_ids_out or n_unique_out; null roots
+ * with the ops or joins form; n < 3 or n > PU_NJ_MAX_N; n_trees < 1 or T (n - 3) >= 2^31; n_rows
+ * outside [0, T]; an unknown form; a tree that is not a binary tree over exactly tips 0 .. n - 1
+ * (pu_fitch_lengths' refusals for the ops and joins forms, pu_fitch_spr_scores' for an edge
+ * list; the message names the tree).
+ * The call is not chunked: the bitsets [T][n-3][nw], the sort's keys and permutations and the
+ * id arrays, T (n - 3) (8 nw + 44) bytes and rocPRIM's temporaries, are on the device at once;
+ * PU_E_NOMEM where they do not fit, or where the host cannot hold the converted trees. */
+#define PU_TREES_OPS 0
+#define PU_TREES_JOINS 1
+#define PU_TREES_EDGES 2
+int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *trees,
+                       const int32_t *roots, int n_rows, int32_t *edge_ids_out,
+                       int64_t *n_unique_out, uint64_t *uniq_bits_out, int32_t *uniq_count_out,
+                       int32_t *rf_out);
+/* Event timing (scripts/time_treeset.py): with pu_treeset_profile(device, 1) every call above
+ * records events between its stages; pu_treeset_kernel_ms returns the last call's times in ms:
+ * the split kernel, the ids (sort, scan, table, counts, edge ids) and the RF stage (the
+ * per-tree sorted lists and the tile kernel). */
+int pu_treeset_profile(int device, int on);
+int pu_treeset_kernel_ms(int device, double *splits_ms, double *ids_ms, double *rf_ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

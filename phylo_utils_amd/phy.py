@@ -82,7 +82,15 @@ trees of FILE follow, every tree's branch lengths are optimised (``--optimise`` 
 one), and after the ``lnL = `` line come a header and one line per tree, ``tree i: lnL deltaL
 bp-RELL p-KH p-SH c-ELW p-AU`` over R RELL replicates (default 10000, the seed of ``--seed``),
 every value from bp-RELL on followed by ``+`` (the tree stays in the 95 % set of that test) or
-``-`` (rejected); ``--no-au`` skips the multiscale replicates and prints p-AU as ``-``.
+``-`` (rejected); ``--no-au`` skips the multiscale replicates and prints p-AU as ``-``;
+``--bootstrap R --consensus FILE [--consensus-threshold P]`` (with ``--nj``) also writes the
+majority-rule consensus of the R replicate trees to FILE (``phylo_utils_amd.treeset``): the splits
+held by more than the share P of the replicates (default 0.5; 1.0: by all of them, the strict
+consensus), every internal node labelled with its split's share in percent, no branch lengths;
+``--compare-trees FILE`` compares the run's final tree (tree 0) with the Newick trees of FILE, one
+per line (trees 1, 2, ...): after the ``lnL = `` line (and the ``--test-trees`` table) come one line
+``rf i: d_0 d_1 ...`` per tree, its Robinson-Foulds distances to all of them, and ``topologies = k
+distinct of m``.
 """
 from __future__ import annotations
 
@@ -268,6 +276,18 @@ def parse_cli(argv=None):
                          "--seed)")
     ap.add_argument("--no-au", action="store_true", dest="no_au",
                     help="with --test-trees: no multiscale replicates; p-AU is printed as '-'")
+    ap.add_argument("--consensus", type=str, default=None, metavar="FILE",
+                    help="with --bootstrap: write the majority-rule consensus of the replicate "
+                         "trees, labelled with the splits' shares in percent, to FILE")
+    ap.add_argument("--consensus-threshold", type=float, default=0.5, metavar="P",
+                    dest="consensus_threshold",
+                    help="with --consensus: keep the splits in more than the share P of the "
+                         "replicates (0.5 to 1; 1: in all of them; default 0.5)")
+    ap.add_argument("--compare-trees", type=str, default=None, metavar="FILE",
+                    dest="compare_trees",
+                    help="after the lnL line: Robinson-Foulds distances between the final tree "
+                         "(tree 0) and the Newick trees of FILE, and the number of distinct "
+                         "topologies among them")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -349,6 +369,16 @@ def validate_args(args):
             raise ValueError("--support excludes --simulate and --distances")
         if args.support < 1:
             raise ValueError("--support needs at least one replicate")
+    if getattr(args, "consensus", None) is not None:
+        if getattr(args, "bootstrap", None) is None:
+            raise ValueError("--consensus needs --bootstrap")
+        if not 0.5 <= getattr(args, "consensus_threshold", 0.5) <= 1.0:
+            raise ValueError("--consensus-threshold needs a share within [0.5, 1]")
+    if getattr(args, "compare_trees", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--compare-trees excludes --simulate and --distances")
+        if not os.path.exists(args.compare_trees):
+            raise FileNotFoundError("Tree file {} does not exist".format(args.compare_trees))
     if getattr(args, "bootstrap", None) is not None:
         if getattr(args, "nj", None) is None:
             raise ValueError("--bootstrap needs --nj")
@@ -426,7 +456,22 @@ def run(args, out=None):
         return None
     if nj is not None:  # --nj: the tree from the alignment's own distances
         if getattr(args, "bootstrap", None) is not None:
-            tree, _, _ = tm.bootstrap_nj(args.bootstrap, seed=args.seed, method=nj)
+            want = getattr(args, "consensus", None) is not None
+            res = tm.bootstrap_nj(args.bootstrap, seed=args.seed, method=nj,
+                                  return_replicates=want)
+            tree = res[0]
+            if want:
+                from . import treeset
+                if res[2] != args.bootstrap:  # such a replicate's tree is unspecified
+                    raise ValueError("--consensus: {} of the {} replicates have a distance that "
+                                     "is not finite".format(args.bootstrap - res[2],
+                                                            args.bootstrap))
+                reps = res[3]
+                names = sorted(tm.names, key=tm.names.get)
+                res = treeset.compare(reps, names=names, rows=0, device=args.device, form="joins")
+                cons = treeset.consensus(res, getattr(args, "consensus_threshold", 0.5))
+                with open(args.consensus, "w") as fh:
+                    fh.write(cons.as_newick() + "\n")
         else:
             tree = tm.set_nj_tree(method=nj)
         if args.output:
@@ -521,7 +566,24 @@ def run(args, out=None):
     out.write("lnL = {}\n".format(lnl))
     for line in table:
         out.write(line + "\n")
+    if getattr(args, "compare_trees", None) is not None:
+        for line in run_compare_trees(args, tm):
+            out.write(line + "\n")
     return lnl
+
+
+def run_compare_trees(args, tm):
+    """--compare-trees: the ``rf i:`` lines and the ``topologies =`` line of the run's final tree
+    (tree 0) and the trees of the file."""
+    from . import treeset
+    with open(args.compare_trees) as fh:
+        trees = [tm.tree] + [line.strip() for line in fh if line.strip()]
+    names = sorted(tm.names, key=tm.names.get)
+    res = treeset.compare(trees, names=names, device=args.device)
+    lines = ["rf {}: {}".format(i, " ".join(str(int(d)) for d in row))
+             for i, row in enumerate(res.rf)]
+    k = len(set(int(c) for c in treeset.topology_classes(res)))
+    return lines + ["topologies = {} distinct of {}".format(k, len(trees))]
 
 
 def run_test_trees(args, tm, first):

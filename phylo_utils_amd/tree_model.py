@@ -776,7 +776,7 @@ class TreeModel(object):
                                        device=self.device)
 
     def set_parsimony_tree(self, n_rep=1, seed=0, min_length=1e-8, spr_rounds=None,
-                           spr_radius=None):
+                           spr_radius=None, return_classes=False):
         """A starting tree by randomised stepwise addition under Fitch parsimony
         (``parsimony.stepwise_addition``): `n_rep` random addition orders
         (``parsimony.random_orders(n, n_rep, seed)``), the shortest tree kept, ties to the lowest
@@ -786,7 +786,10 @@ class TreeModel(object):
         the shortest refined tree is kept.  Every branch length is ``max(edge change count / sum
         of siteweights, min_length)``.  Needs coded tips and no model at all, so it also serves
         the non-reversible models ``set_nj_tree`` refuses.  Calls ``set_tree``; returns (tree,
-        length, the lengths of all replicates)."""
+        length, the lengths of all replicates), and with `return_classes` also
+        ``treeset.topology_classes`` of the `n_rep` (refined) trees, int [n_rep]: for each the
+        index of the first replicate with the same topology, so ``len(set(classes))`` is the
+        number of distinct topologies the replicates reached."""
         from . import parsimony
         aln = self._coded_alignment()
         w = parsimony.integer_weights(self.siteweights, aln[0].shape[1])
@@ -801,23 +804,57 @@ class TreeModel(object):
                                               device=self.device)
         tree = parsimony.edge_lengths_tree(tree, aln[2], per_edge, int(w.sum()), min_length)
         self.set_tree(tree)
+        if return_classes:
+            from . import treeset
+            classes = treeset.topology_classes(
+                treeset.compare(edges, rows=0, device=self.device, want_table=False))
+            return tree, int(lengths[best]), lengths, classes
         return tree, int(lengths[best]), lengths
 
-    def bootstrap_nj(self, n_replicates=100, seed=0, method="nj", **distance_kw):
+    def bootstrap_nj(self, n_replicates=100, seed=0, method="nj", return_replicates=False,
+                     **distance_kw):
         """``set_nj_tree`` with bootstrap support (``bootstrap.bootstrap_nj`` on the model's own
         alignment and models): the reference tree becomes the model's tree, as ``set_nj_tree``
         sets it, with every internal node that carries one of its splits labelled with the
         split's support in percent over `n_replicates` resampled alignments.  Returns (tree,
-        support [n-3] of clusters n + m in join order, n_ok: the replicates counted)."""
+        support [n-3] of clusters n + m in join order, n_ok: the replicates counted), and with
+        `return_replicates` also (joins [R][n-2][2], roots [R][2]) of the replicate trees, rows
+        in alignment order: a tree set for ``treeset.compare`` (``form="joins"``) as long as
+        ``n_ok`` equals `n_replicates` (the tree of a replicate that is not ok is unspecified)."""
         from . import bootstrap
         codes, table, names = self._coded_alignment()
         distance_kw.setdefault("device", self.device)
         distance_kw.setdefault("weights", np.asarray(self.siteweights, dtype=np.float64))
-        tree, support, n_ok = bootstrap.bootstrap_nj(
+        out = bootstrap.bootstrap_nj(
             (codes, table, names), self.substitution_model, getattr(self, "rate_model", None),
-            n_replicates=n_replicates, seed=seed, method=method, min_length=1e-8, **distance_kw)
-        self.set_tree(tree)
-        return tree, support, n_ok
+            n_replicates=n_replicates, seed=seed, method=method, min_length=1e-8,
+            return_replicates=bool(return_replicates), **distance_kw)
+        self.set_tree(out[0])
+        return out
+
+    def rf_distance(self, other):
+        """The Robinson-Foulds distance between the model's current tree and `other` (a
+        ``Tree`` or Newick over the same names), an int (``treeset.rf_distances``)."""
+        from . import treeset
+        if getattr(self, "tree", None) is None:
+            raise ValueError("No tree has been set")
+        names = sorted(self.names, key=self.names.get)
+        return int(treeset.rf_distances([self.tree, other], names, device=self.device)[0, 1])
+
+    def map_support(self, trees):
+        """Label the model's current tree with the support of the tree set `trees` -- any form
+        ``treeset.compare`` takes, arrays over the alignment's rows: the replicates of
+        ``bootstrap_nj(return_replicates=True)``, a list of Newick strings, edge lists -- through
+        ``treeset.support``.  Returns (support [2n-3] per edge of the tree in op order, NaN on
+        pendant edges, the labelled copy of the tree with the model's current branch
+        lengths); the model's own tree is left as it is."""
+        from . import treeset
+        from .tree import with_lengths
+        if getattr(self, "tree", None) is None:
+            raise ValueError("No tree has been set")
+        names = sorted(self.names, key=self.names.get)
+        current = with_lengths(self.tree, self.traversal.brlens)
+        return treeset.support(current, trees, names=names, device=self.device)
 
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
