@@ -994,6 +994,55 @@ int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *
 int pu_treeset_profile(int device, int on);
 int pu_treeset_kernel_ms(int device, double *splits_ms, double *ids_ms, double *rf_ms);
 
+/* ---- Site concordance factors (normative; tests/concordance_reference.py
+ * restates it) ----
+ * The reference has no concordance factors; the rule is this project's own.  The alignment
+ * arguments are pu_fitch_lengths'; the tree is an edge list edges [2 n_taxa - 3][2] in DESIGN
+ * 4.22's form (tips 0 .. n_taxa - 1 are the alignment's rows, internal nodes n_taxa ..
+ * 2 n_taxa - 3), 4 <= n_taxa <= PU_PARS_MAX_TAXA.
+ * Edge e = (x, y) is internal iff both ends are internal nodes.  x's other two edges, in
+ * increasing edge id, lead away from e to clades A and B, y's to C and D; a clade is the set of
+ * tips beyond its edge, in ascending row order.  With Q = n_quartets and m = |A||B||C||D| (64
+ * bits): if m <= Q the branch has nq[e] = m quartets, all of them, quartet q the mixed-radix
+ * number (ia, ib, ic, id), id fastest, of the tips' indices in their clades; else nq[e] = Q and
+ * clade k = 0..3 (A, B, C, D) of quartet q takes the tip at index min(floor(u |X|), |X| - 1) of
+ * its clade X, u = philox_u(seed, g = q, c2 = 4 e + k, c3 = 2): Philox4x32-10 as DESIGN 4.10
+ * defines u, counter word 3 = 2 (the simulator uses 0, the bootstrap 1).  Tips are drawn with
+ * replacement across quartets; quartet q of branch e depends on (seed, e, q, the clades) alone.
+ * A pattern p of weight w_p is decisive for a quartet (a, b, c, d) iff the state sets of all four
+ * codes are singletons (a gap and every ambiguity code is not); with s the four states,
+ *   n1 += w_p where sa = sb, sc = sd, sa != sc   (ab|cd, the branch itself)
+ *   n2 += w_p where sa = sc, sb = sd, sa != sb   (ac|bd)
+ *   n3 += w_p where sa = sd, sb = sc, sa != sb   (ad|bc)
+ * counts_out [2 n_taxa - 3][Q][3] = (n1, n2, n3), nq_out [2 n_taxa - 3], taxa_out (nullable)
+ * [2 n_taxa - 3][Q][4] the picks; rows of edges that are not internal and slots q >= nq[e] are
+ * zero, their taxa -1.  Every sum is an unsigned 64-bit integer: no result depends on the launch
+ * shape, on PU_SCF_FEED or on the chunking.  The finish (sCF = 100 mean(n1 / (n1 + n2 + n3))
+ * over the quartets with a decisive pattern, and so on) is the caller's, in float64
+ * (phylo_utils_amd/concordance.py).
+ * PU_E_ARG, before any device is touched: everything pu_fitch_lengths refuses of the alignment,
+ * n_taxa < 4, a null edges, counts_out or nq_out, n_quartets < 1, an edge list that is not a
+ * binary tree over the rows (pu_fitch_spr_scores' refusals), and an n_quartets whose counts and
+ * picks of one branch alone (40 bytes per quartet) pass half the workspace.
+ * The workspace obeys the 256 MiB rule of the parsimony calls (PU_SCF_WS=bytes lowers it): half
+ * for the counts and picks of a chunk of branches, half for the state bytes [taxon][pattern]
+ * of a chunk of patterns; the call is cut into chunks of branches and, inside each, of
+ * patterns.  PU_SCF_CHUNK=n, read at each call, caps the branches of a chunk.  A chunk of
+ * patterns is never less than one tile of 2048: a PU_SCF_WS below 2 * 2048 n_taxa bytes is
+ * exceeded by that much and no further.
+ * PU_SCF_FEED=lds|global, read at each call, selects how k_scf_counts is fed: the pattern tile
+ * of all rows staged in LDS (tiles of 2048, 1024 or 512 patterns for n_taxa <= 74, 148 or 296;
+ * beyond, as global), or the rows read from memory. */
+int pu_scf_counts(int device, int n_taxa, int64_t n_pat, int n_codes, int n_states,
+                  const uint8_t *codes, const double *code_table, const int64_t *weights,
+                  const int32_t *edges, int n_quartets, uint64_t seed, uint64_t *counts_out,
+                  int32_t *nq_out, int32_t *taxa_out);
+/* Event timing (scripts/time_concordance.py): with pu_scf_profile(device, 1) the call above
+ * records events around its launches; pu_scf_kernel_ms returns the last call's times in ms,
+ * summed over its chunks: the pick kernel, the state-byte kernel and k_scf_counts. */
+int pu_scf_profile(int device, int on);
+int pu_scf_kernel_ms(int device, double *picks_ms, double *states_ms, double *counts_ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -90,7 +90,16 @@ consensus), every internal node labelled with its split's share in percent, no b
 ``--compare-trees FILE`` compares the run's final tree (tree 0) with the Newick trees of FILE, one
 per line (trees 1, 2, ...): after the ``lnL = `` line (and the ``--test-trees`` table) come one line
 ``rf i: d_0 d_1 ...`` per tree, its Robinson-Foulds distances to all of them, and ``topologies = k
-distinct of m``.
+distinct of m``;
+``--scf [Q]`` and ``--gcf FILE`` (after ``-t``, ``--nj`` or ``--parsimony``, on the final tree, after
+``--support``) label every internal edge with concordance factors (``phylo_utils_amd.concordance``):
+the site concordance factor over up to Q quartets per branch (default 100, the seed of ``--seed``)
+and the gene concordance factor in the Newick trees of FILE, one per line, all over the
+alignment's taxa.  The labels of an internal node are joined by ``/`` in the fixed order SH-aLRT,
+aBayes, gCF, sCF, of those asked for (concordance factors in percent with one decimal, ``NA`` where
+no quartet has a decisive site), and ``-o`` receives that Newick; ``--cf-table FILE`` writes a TSV
+with a header and one row per internal edge: ``id gCF gDF1 gDF2 gDFP gN sCF sDF1 sDF2 sN length``,
+``id`` the edge's number in the tree's op order, ``NA`` for what was not asked for.
 """
 from __future__ import annotations
 
@@ -288,6 +297,15 @@ def parse_cli(argv=None):
                     help="after the lnL line: Robinson-Foulds distances between the final tree "
                          "(tree 0) and the Newick trees of FILE, and the number of distinct "
                          "topologies among them")
+    ap.add_argument("--scf", type=int, nargs="?", const=100, default=None, metavar="Q",
+                    help="label the internal edges of the final tree with site concordance "
+                         "factors over up to Q quartets per branch (default 100; seed: --seed)")
+    ap.add_argument("--gcf", type=str, default=None, metavar="FILE",
+                    help="label the internal edges of the final tree with gene concordance "
+                         "factors in the Newick trees of FILE (one per line)")
+    ap.add_argument("--cf-table", type=str, default=None, metavar="FILE", dest="cf_table",
+                    help="with --scf or --gcf: write a TSV with one row per internal edge (id, "
+                         "gCF, gDF1, gDF2, gDFP, gN, sCF, sDF1, sDF2, sN, length)")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -334,7 +352,7 @@ def validate_args(args):
                 getattr(args, "parsimony", None) is None:
             # no tree of the run's own: the candidates alone
             for name in ("optimise", "nni", "spr", "fit", "place", "support", "ancestral",
-                         "site_rates", "parsimony_score"):
+                         "site_rates", "parsimony_score", "scf", "gcf"):
                 if getattr(args, name, None) not in (None, 0, False):
                     raise ValueError("--{} needs a tree (-t, --nj or --parsimony)".format(
                         name.replace("_", "-")))
@@ -379,6 +397,16 @@ def validate_args(args):
             raise ValueError("--compare-trees excludes --simulate and --distances")
         if not os.path.exists(args.compare_trees):
             raise FileNotFoundError("Tree file {} does not exist".format(args.compare_trees))
+    if getattr(args, "cf_table", None) is not None and getattr(args, "scf", None) is None \
+            and getattr(args, "gcf", None) is None:
+        raise ValueError("--cf-table needs --scf or --gcf")
+    if getattr(args, "scf", None) is not None or getattr(args, "gcf", None) is not None:
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
+            raise ValueError("--scf and --gcf exclude --simulate and --distances")
+        if getattr(args, "scf", None) is not None and args.scf < 1:
+            raise ValueError("--scf needs at least one quartet per branch")
+        if getattr(args, "gcf", None) is not None and not os.path.exists(args.gcf):
+            raise FileNotFoundError("Tree file {} does not exist".format(args.gcf))
     if getattr(args, "bootstrap", None) is not None:
         if getattr(args, "nj", None) is None:
             raise ValueError("--bootstrap needs --nj")
@@ -539,6 +567,15 @@ def run(args, out=None):
         if args.output:
             with open(args.output, "w") as fh:
                 fh.write(tree.as_newick() + "\n")
+        support_labels = {int(q[0]): support_label(a, b)
+                          for q, a, b in zip(quartets, sup["sh_alrt"], sup["abayes"])}
+    else:
+        support_labels = None
+    if getattr(args, "scf", None) is not None or getattr(args, "gcf", None) is not None:
+        tree = run_concordance(args, tm, support_labels)
+        if args.output:
+            with open(args.output, "w") as fh:
+                fh.write(tree.as_newick() + "\n")
     if getattr(args, "ancestral", None) is not None:
         seqs, newick = tm.ancestral_sequences(alphabet)
         with open(args.ancestral, "w") as fh:
@@ -570,6 +607,40 @@ def run(args, out=None):
         for line in run_compare_trees(args, tm):
             out.write(line + "\n")
     return lnl
+
+
+def run_concordance(args, tm, support_labels):
+    """--scf / --gcf / --cf-table: the final tree with its labels -- `support_labels` ({node
+    index: SH-aLRT/aBayes} or None), then gCF, then sCF -- and the table."""
+    from . import concordance
+    from .tree import with_lengths
+    trees = None
+    if getattr(args, "gcf", None) is not None:
+        with open(args.gcf) as fh:
+            trees = [line.strip() for line in fh if line.strip()]
+        if not trees:
+            raise ValueError("--gcf: {} holds no tree".format(args.gcf))
+    if getattr(args, "scf", None) is not None:
+        res = tm.concordance_factors(trees=trees, n_quartets=args.scf, seed=args.seed)
+    else:
+        names = sorted(tm.names, key=tm.names.get)
+        res = concordance.gene_concordance(tm.tree, trees, names=names, device=args.device,
+                                           _prepared=True)
+    current = with_lengths(tm.tree, tm.traversal.brlens)
+    if getattr(args, "cf_table", None) is not None:
+        cols = ("gCF", "gDF1", "gDF2", "gDFP", "gN", "sCF", "sDF1", "sDF2", "sN")
+        with open(args.cf_table, "w") as fh:
+            fh.write("\t".join(("id",) + cols + ("length",)) + "\n")
+            for i, e in enumerate(res.internal):
+                row = [str(int(e))]
+                for c in cols:
+                    v = getattr(res, c)
+                    row.append("NA" if v is None else
+                               str(int(v[i])) if c == "gN" else
+                               concordance.format_value(float(v[i]), "%.10g"))
+                row.append("{:.10g}".format(float(tm.traversal.brlens[res.pairs[int(e)]])))
+                fh.write("\t".join(row) + "\n")
+    return concordance.label_tree(current, res, prefix=support_labels)
 
 
 def run_compare_trees(args, tm):

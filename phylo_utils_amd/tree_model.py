@@ -856,6 +856,28 @@ class TreeModel(object):
         current = with_lengths(self.tree, self.traversal.brlens)
         return treeset.support(current, trees, names=names, device=self.device)
 
+    def concordance_factors(self, trees=None, n_quartets=100, seed=0):
+        """The concordance factors of every internal branch of the model's tree (DESIGN 4.29,
+        ``phylo_utils_amd.concordance``): the site factors on the model's own alignment and
+        ``siteweights`` (``concordance.site_concordance``: up to `n_quartets` quartets per
+        branch, drawn under `seed`) and, when `trees` is given -- any form ``treeset.compare``
+        takes, over the alignment's rows -- the gene factors in that tree set
+        (``concordance.gene_concordance``).  One ``ConcordanceResult``, its edges the tree's in
+        op order, its ``pairs`` the model's own node indices.  Needs coded tips and no
+        substitution model, so it serves the non-reversible models too; the likelihood state is
+        left as it is."""
+        from . import concordance
+        if getattr(self, "tree", None) is None:
+            raise ValueError("No tree has been set")
+        aln = self._coded_alignment()
+        res = concordance.site_concordance(aln, self.tree, n_quartets=n_quartets, seed=seed,
+                                           weights=self.siteweights, device=self.device,
+                                           _prepared=True)
+        if trees is not None:
+            res = concordance.merge(res, concordance.gene_concordance(
+                self.tree, trees, names=aln[2], device=self.device, _prepared=True))
+        return res
+
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
         self._ensure()

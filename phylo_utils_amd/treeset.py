@@ -123,6 +123,16 @@ def _batch(trees, names, form):
                      "edge batch [T][2n-3][2]")
 
 
+def edge_lists(trees, names=None, form=None):
+    """(edges int32 [T][2n-3][2], names): every tree of a tree set -- any form ``compare`` takes
+    -- as (child end, parent end) node pairs in its form's own edge order, what
+    ``TreeSetResult.edges`` holds, without a device call."""
+    form, a, roots, names, _ = _batch(trees, names, form)
+    if form == "edges":
+        return a, names
+    return _op_edges(a if form == "ops" else _joins_as_ops(a), roots), names
+
+
 def compare(trees, names=None, rows=None, device=0, form=None, want_table=True):
     """pu_treeset_compare: the ``TreeSetResult`` of a tree set.  `rows` None: the full RF matrix
     [T][T]; an integer k: trees 0..k-1 against all, [k][T]; 0: no distances.  `want_table` False
