@@ -1043,6 +1043,91 @@ int pu_scf_counts(int device, int n_taxa, int64_t n_pat, int n_codes, int n_stat
 int pu_scf_profile(int device, int on);
 int pu_scf_kernel_ms(int device, double *picks_ms, double *states_ms, double *counts_ms);
 
+/* ---- likelihood mapping -------------------------------------------------- */
+/* The reference has no likelihood mapping (Strimmer & von Haeseler 1997); the rule is this
+ * project's own.  Alignment and model as in pu_pair_distances: codes [n_taxa][n_sites] below
+ * n_codes <= 32, rows of code_table [n_codes][K], K in {2, 4, 20}, pattern weights (NULL: 1), a
+ * reversible model's eigen-system and 1 <= n_cat <= PU_PAIR_MAX_CAT categories (a zero rate is
+ * an ordinary category).  quartets [Q][4] are four distinct taxa (a, b, c, d).  Topology tau has
+ * tips (p, q | r, s) = (a, b | c, d), (a, c | b, d), (a, d | b, c) for tau = 0, 1, 2 and lengths
+ * (l_p, l_q, l_r, l_s, l_i), l_i the internal edge; with P_c(t) = E diag(e^{lambda r_c t}) E^-1
+ *   L_s = sum_c q_c sum_i pi_i (P_c(l_p) x_p)_i (P_c(l_q) x_q)_i
+ *                   sum_j P_c(l_i)[i][j] (P_c(l_r) x_r)_j (P_c(l_s) x_s)_j
+ *   lnL = sum_s w_s log L_s        (no scaler; w_s > 0 and L_s <= 0 give -inf; w_s >= 0)
+ * and derivatives in one length as pu_edge_derivs defines them (the factor r_c included).
+ * The optimiser: the start is t0[5] (NULL: 0.1 each) and one evaluation there; a round takes the
+ * edges in the order p, q, r, s, i, each by the Newton rule of pu_optimise_edge (tol, max_iter,
+ * the bounds 1e-8 and 100) from its current length with the others fixed; after a round it stops
+ * at round == max_rounds or, where min_gain >= 0, at lnL_after - lnL_before_round <= min_gain
+ * (min_gain < 0: never early); max_rounds = 0 is the one evaluation; a non-finite lnL ends the
+ * topology at once.
+ * out [Q][3][8] = (lnL, l_p, l_q, l_r, l_s, l_i, rounds, evaluations), the evaluations being the
+ * start's and those of the Newton rule; derivs (nullable) [Q][3][5][2] = (lnL', lnL'') in each
+ * length at the final lengths, in the order p, q, r, s, i (NaN after a non-finite lnL).
+ * Results are bitwise repeatable and do not depend on the chunking of the quartets, on the grid
+ * or on the other quartets of the call; no floating-point atomics (DESIGN 4.30 states the order
+ * of every sum).
+ * Two feeds of the optimiser, PU_LMAP_FEED=bins|patterns read at each call: `patterns` walks the
+ * four code rows; `bins` first counts per quartet the weighted 4-tuples of the codes in use in
+ * unsigned 64-bit integers and runs over the non-zero bins.  The bins need n_used^4 <= 4096 and
+ * non-negative integer weights below 2^53: the host form checks both and takes the patterns
+ * otherwise; the device form takes n_codes^4 <= 4096 and, for integer weights, the caller's word:
+ * without weights it defaults to the bins, with weights to the patterns unless PU_LMAP_FEED=bins
+ * states them integer.  The bins of a chunk of quartets stay within 256 MiB;
+ * PU_LMAP_CHUNK=<quartets>, read at each call, lowers the chunk.
+ * PU_E_ARG, before any device is touched: a null buffer, n_taxa < 4, n_sites <= 0, n_codes
+ * outside [1, 32], n_states not 2, 4 or 20, n_cat outside [1, PU_PAIR_MAX_CAT], tables past the
+ * 160 KiB of LDS of one workgroup (8 (2 K^2 + 2 K + 2 C + n K + 6 C n K + C K^2 + 3 C K + 24)
+ * bytes, n the codes), Q < 1, a quartet index out of range or repeated within a quartet,
+ * tol <= 0, max_iter < 0, max_rounds < 0, a NaN min_gain, a t0 outside [1e-8, 100], and -- host
+ * forms -- a code >= n_codes and a weight that is negative or not finite.  The device form
+ * cannot look at its buffers: codes below n_codes and weights >= 0 are its preconditions, and
+ * the result of a call that breaks them is not defined (the patterns feed gives -inf for a code
+ * >= n_codes, the bins feed does not count the pattern). */
+int pu_lmap_scores(int device, int n_states, int n_cat, int n_codes, const double *code_table,
+                   const double *evecs, const double *evals, const double *ivecs,
+                   const double *freqs, const double *rates, const double *cat_weights,
+                   const uint8_t *codes, int n_taxa, int64_t n_sites, const double *site_weights,
+                   int64_t n_quartets, const int32_t *quartets, const double *t0, double tol,
+                   int max_iter, int max_rounds, double min_gain, double *out, double *derivs);
+/* The same on device buffers -- the output of pu_simulate_device or pu_compress_patterns_device
+ * with no copy: d_codes rows ld bytes apart (ld >= n_sites), d_site_weights (nullable), d_out
+ * and d_derivs (nullable) on the device; quartets and the model on the host.  Asynchronous on
+ * the caller's stream. */
+int pu_lmap_scores_device(int device, void *stream, int n_states, int n_cat, int n_codes,
+                          const double *code_table, const double *evecs, const double *evals,
+                          const double *ivecs, const double *freqs, const double *rates,
+                          const double *cat_weights, const uint8_t *d_codes, int64_t ld,
+                          int n_taxa, int64_t n_sites, const double *d_site_weights,
+                          int64_t n_quartets, const int32_t *quartets, const double *t0,
+                          double tol, int max_iter, int max_rounds, double min_gain,
+                          double *d_out, double *d_derivs);
+/* The statistic of the bins feed: bins_out [Q][n_used^4], entry ((u_a n_used + u_b) n_used +
+ * u_c) n_used + u_d = the sum of the weights of the patterns where the quartet's taxa show the
+ * codes used[u_a], used[u_b], used[u_c], used[u_d].  `used` lists n_used ascending codes (NULL:
+ * all n_codes).  Exact.  PU_E_ARG as above, and for n_used^4 > 4096, a weight that is no
+ * non-negative integer below 2^53, a `used` that is not ascending, and a code outside it. */
+int pu_lmap_bins(int device, const uint8_t *codes, int n_taxa, int64_t n_sites, int n_codes,
+                 const double *site_weights, int64_t n_quartets, const int32_t *quartets,
+                 int n_used, const uint8_t *used, uint64_t *bins_out);
+/* The quartets of a mapping, Philox as DESIGN 4.10 defines u, counter word 3 = 3.  Without
+ * clusters (cluster NULL), m = C(n_taxa, 4): m <= n_quartets gives all a < b < c < d in
+ * lexicographic order; else quartet g draws r_k = min(floor(u_k (n - k)), n - k - 1), u_k =
+ * philox_u(seed, g, k, 3), k = 0..3, and its taxon k is r_k raised by one for each earlier taxon
+ * of the quartet <= it, those taken in ascending order; (a, b, c, d) is the draw order.  With
+ * cluster [n_taxa] in {-1, 0, 1, 2, 3}: a from cluster 0, b from 1, c from 2, d from 3, m the
+ * product of the sizes; m <= n_quartets gives all, mixed radix with d fastest over the
+ * ascending members; else the member at index min(floor(u |X|), |X| - 1), u = philox_u(seed, g,
+ * 4 + k, 3).  quartets_out [min(m, n_quartets)][4] (room for n_quartets), *n_out their number.
+ * PU_E_ARG: n_taxa < 4, n_quartets < 1, a null output, a cluster value outside -1..3, an empty
+ * cluster. */
+int pu_lmap_quartets(int device, int n_taxa, const int32_t *cluster, int64_t n_quartets,
+                     uint64_t seed, int32_t *quartets_out, int64_t *n_out);
+/* Event timing (scripts/time_lmap.py), as pu_pair_profile / pu_pair_kernel_ms: the bin launches
+ * and the optimiser launches of the last pu_lmap_scores* call, summed over its chunks. */
+int pu_lmap_profile(int device, int on);
+int pu_lmap_kernel_ms(int device, double *bins_ms, double *opt_ms);
+
 /* ---- multi-device / stream interop (site sharding) ------------------- */
 /* Launch on the caller's HIP stream (hipStream_t as void*), e.g.
  * torch.cuda.current_stream().cuda_stream, so the RCCL all-reduce of the lnL is

@@ -189,6 +189,16 @@ SIGNATURES = {
                                _c_u64, _P, _P, _P]),
     "pu_scf_profile": (_c_int, [_c_int, _c_int]),
     "pu_scf_kernel_ms": (_c_int, [_c_int, _P, _P, _P]),
+    "pu_lmap_scores": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _c_int, _c_i64, _P, _c_i64, _P, _P, _c_dbl, _c_int, _c_int,
+                                _c_dbl, _P, _P]),
+    "pu_lmap_scores_device": (_c_int, [_c_int, _P, _c_int, _c_int, _c_int, _P, _P, _P, _P, _P, _P,
+                                       _P, _P, _c_i64, _c_int, _c_i64, _P, _c_i64, _P, _P, _c_dbl,
+                                       _c_int, _c_int, _c_dbl, _P, _P]),
+    "pu_lmap_bins": (_c_int, [_c_int, _P, _c_int, _c_i64, _c_int, _P, _c_i64, _P, _c_int, _P, _P]),
+    "pu_lmap_quartets": (_c_int, [_c_int, _c_int, _P, _c_i64, _c_u64, _P, _P]),
+    "pu_lmap_profile": (_c_int, [_c_int, _c_int]),
+    "pu_lmap_kernel_ms": (_c_int, [_c_int, _P, _P]),
     "pu_ctx_stream": (_P, [_P]),
     "pu_ctx_device_bytes": (_c_i64, [_P]),
     "pu_write_ceiling": (_c_int, [_c_int, _c_i64, _c_int, _P]),

@@ -3,8 +3,9 @@
 // newton_start() names the first abscissa to evaluate, newton_step() takes lnL and its two
 // derivatives there and names the next one, until `done`.  One definition serves every driver:
 // the host loop over k_edge launches (pu_edge.cpp), the combiner of the persistent k_edge_newton
-// launch (pu_edge.hip), the three arrangements that advance per k_quartet launch (pu_nni.hip) and
-// the loop inside k_place_newton (pu_place.hip).  No contraction into fused multiply-adds: the
+// launch (pu_edge.hip), the three arrangements that advance per k_quartet launch (pu_nni.hip),
+// the loop inside k_place_newton (pu_place.hip) and the five-length rounds inside k_lmap_opt
+// (pu_lmap.hip).  No contraction into fused multiply-adds: the
 // arithmetic is that of tests/newton_reference.py, operation for operation.
 #pragma once
 

@@ -1,6 +1,7 @@
 // pu_philox.h -- the one copy of the counter-based generator behind every draw of this library
 // (pu_simulate.hip: DESIGN 4.10, counter word 3 = 0; pu_bootstrap.hip: DESIGN 4.14, counter
-// word 3 = 1).  Not part of the public ABI.
+// word 3 = 1; pu_scf.hip: DESIGN 4.29, counter word 3 = 2; pu_lmap.hip: DESIGN 4.30, counter
+// word 3 = 3).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

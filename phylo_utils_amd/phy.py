@@ -91,6 +91,14 @@ consensus), every internal node labelled with its split's share in percent, no b
 per line (trees 1, 2, ...): after the ``lnL = `` line (and the ``--test-trees`` table) come one line
 ``rf i: d_0 d_1 ...`` per tree, its Robinson-Foulds distances to all of them, and ``topologies = k
 distinct of m``;
+``-s aln.fasta -m MODEL --lmap [Q]`` needs no ``-t`` either: likelihood mapping
+(``phylo_utils_amd.lmap``) of Q quartets (default min(C(n,4), 25 n), the seed of
+``--seed``; with ``--lmap-clusters FILE``, four lines of taxon names, one taxon of each line per
+quartet).  It prints ``lmap: quartets = ...``, one ``lmap: region k = count (pct %)`` line per
+region 1-7 (the three corners, the three edges, the centre) and a ``lmap: resolved ... partly ...
+unresolved ...`` line; ``--lmap-table FILE`` writes a TSV with one row per quartet, ``--lmap-svg
+FILE`` the two triangles.
+
 ``--scf [Q]`` and ``--gcf FILE`` (after ``-t``, ``--nj`` or ``--parsimony``, on the final tree, after
 ``--support``) label every internal edge with concordance factors (``phylo_utils_amd.concordance``):
 the site concordance factor over up to Q quartets per branch (default 100, the seed of ``--seed``)
@@ -195,6 +203,9 @@ def build_rate_model(desc):
         alpha = _one(desc["rate_param"])
         return RM.GammaRateModel(ncat, alpha if alpha is not None else 0.5)
     return RM.UniformRateModel()
+
+
+LMAP_DEFAULT = ("default",)  # --lmap without a number: min(C(n, 4), 25 n) quartets (no string: argparse would convert it)
 
 
 def parse_cli(argv=None):
@@ -306,6 +317,19 @@ def parse_cli(argv=None):
     ap.add_argument("--cf-table", type=str, default=None, metavar="FILE", dest="cf_table",
                     help="with --scf or --gcf: write a TSV with one row per internal edge (id, "
                          "gCF, gDF1, gDF2, gDFP, gN, sCF, sDF1, sDF2, sN, length)")
+    ap.add_argument("--lmap", type=int, nargs="?", const=LMAP_DEFAULT, default=None, metavar="Q",
+                    help="likelihood mapping of -s (no -t): fit the three trees of Q quartets "
+                         "(default min(C(n,4), 25 n); seed: --seed) and print the shares of the "
+                         "seven regions of the triangle")
+    ap.add_argument("--lmap-clusters", type=str, default=None, metavar="FILE",
+                    dest="lmap_clusters",
+                    help="with --lmap: four lines of taxon names; every quartet takes one taxon "
+                         "of each line")
+    ap.add_argument("--lmap-table", type=str, default=None, metavar="FILE", dest="lmap_table",
+                    help="with --lmap: write a TSV with one row per quartet (taxa, three lnL, "
+                         "three weights, regions)")
+    ap.add_argument("--lmap-svg", type=str, default=None, metavar="FILE", dest="lmap_svg",
+                    help="with --lmap: draw the two triangles to FILE")
     ap.add_argument("-o", "--output", type=str, default=None,
                     help="output file of --simulate / --distances (default: stdout) / --nj / "
                          "--nni")
@@ -314,6 +338,25 @@ def parse_cli(argv=None):
 
 def validate_args(args):
     """bin/phy.py:22-30."""
+    if getattr(args, "lmap", None) is None:
+        for k in ("lmap_clusters", "lmap_table", "lmap_svg"):
+            if getattr(args, k, None) is not None:
+                raise ValueError("--%s needs --lmap" % k.replace("_", "-"))
+    else:  # a run of its own: it takes no tree and nothing that makes or works on one
+        if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None \
+                or args.tree is not None or getattr(args, "nj", None) is not None \
+                or getattr(args, "parsimony", None) is not None:
+            raise ValueError("--lmap excludes --distances, --simulate, -t, --nj and --parsimony")
+        if args.lmap != LMAP_DEFAULT and args.lmap < 1:
+            raise ValueError("--lmap needs at least one quartet")
+        if args.alignment is None:
+            raise ValueError("Alignment file not specified")
+        if not os.path.exists(args.alignment):
+            raise FileNotFoundError("Alignment file {} does not exist".format(args.alignment))
+        cl = getattr(args, "lmap_clusters", None)
+        if cl is not None and not os.path.exists(cl):
+            raise FileNotFoundError("Cluster file {} does not exist".format(cl))
+        return
     if getattr(args, "parsimony_spr", None) is not None:
         if getattr(args, "parsimony", None) is None:
             raise ValueError("--parsimony-spr needs --parsimony")
@@ -711,6 +754,40 @@ def run_distances(args, out=None):
     return names, D, V
 
 
+def read_clusters(path):
+    """--lmap-clusters: four non-empty lines of taxon names, separated by blanks or commas."""
+    with open(path) as fh:
+        groups = [line.replace(",", " ").split() for line in fh if line.strip()]
+    if len(groups) != 4:
+        raise ValueError("{} holds {} lines of names, not four".format(path, len(groups)))
+    return groups
+
+
+def run_lmap(args, out=None):
+    """--lmap: the ``lmap:`` lines of the alignment's likelihood map, and its table and SVG."""
+    from . import lmap
+    out = sys.stdout if out is None else out
+    aln = A.read_fasta(args.alignment)
+    desc = parse_model_string(args.model)
+    alphabet = A.PROTEIN if desc["subs_model"] in PROTEIN_MODELS else A.DNA
+    clusters = None
+    if getattr(args, "lmap_clusters", None) is not None:
+        clusters = read_clusters(args.lmap_clusters)
+    res = lmap.likelihood_mapping(aln, build_model(desc), build_rate_model(desc),
+                                  n_quartets=None if args.lmap == LMAP_DEFAULT else args.lmap,
+                                  seed=args.seed, clusters=clusters,
+                                  alphabet=alphabet, device=args.device)
+    for line in lmap.report_lines(res):
+        out.write(line + "\n")
+    if getattr(args, "lmap_table", None) is not None:
+        with open(args.lmap_table, "w") as fh:
+            lmap.write_table(res, fh)
+    if getattr(args, "lmap_svg", None) is not None:
+        with open(args.lmap_svg, "w") as fh:
+            lmap.write_svg(res, fh)
+    return res
+
+
 def main(argv=None):
     args = parse_cli(argv)
     try:
@@ -719,7 +796,9 @@ def main(argv=None):
         sys.stderr.write("ERROR: {}\n".format(e))
         return 1
     try:
-        if args.distances:
+        if getattr(args, "lmap", None) is not None:
+            run_lmap(args)
+        elif args.distances:
             run_distances(args)
         elif args.simulate is not None:
             run_simulate(args)

@@ -878,6 +878,21 @@ class TreeModel(object):
                 self.tree, trees, names=aln[2], device=self.device, _prepared=True))
         return res
 
+    def likelihood_mapping(self, n_quartets=None, seed=0, clusters=None, **optimiser):
+        """The likelihood map (``phylo_utils_amd.lmap``) of the model's own alignment
+        and ``siteweights`` under its substitution and rate models: `n_quartets` quartets (None:
+        min(C(n, 4), 25 n)) drawn under `seed` -- of the four `clusters` where given: an array
+        over the rows in {-1, 0, 1, 2, 3} or four lists of taxon names -- each fitted under its
+        three topologies.  Returns a ``lmap.LikelihoodMap``.  Needs coded tips and a reversible
+        model, and no tree; the context is not touched.  `optimiser`: t0, tol, max_iter,
+        max_rounds, min_gain of ``lmap.quartet_likelihoods``."""
+        from . import lmap
+        codes, table, names = self._coded_alignment()
+        return lmap.likelihood_mapping(
+            (codes, table, names), self.substitution_model, getattr(self, "rate_model", None),
+            n_quartets=n_quartets, seed=seed, clusters=clusters, device=self.device,
+            weights=np.asarray(self.siteweights, dtype=np.float64), **optimiser)
+
     def likelihood(self):
         """Total lnL = sum of sitewise lnL over alignment columns (bin/phy.py:146)."""
         self._ensure()
