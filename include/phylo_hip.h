@@ -994,6 +994,52 @@ int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *
 int pu_treeset_profile(int device, int on);
 int pu_treeset_kernel_ms(int device, double *splits_ms, double *ids_ms, double *rf_ms);
 
+/* ---- Sets of trees with branch lengths: weighted RF, branch score, path distances, length
+ * sums (normative; tests/treedist_reference.py restates it) ----
+ * The trees, forms, edge orders, splits and ids are pu_treeset_compare's.  lengths [T][2n-3],
+ * fp64, holds every tree's edge lengths in its form's own edge order.  A tree's lengths are
+ * indexed by key: pendant key i is the edge at tip i, split key u the edge whose non-trivial
+ * split has id u; a key the tree does not hold has length 0.
+ *   wRF(a, b)   = sum over keys of |l_a - l_b|; KF2(a, b) = sum over keys of (l_a - l_b)^2 (the
+ *                 branch score is its square root, left to the caller).  Sum order of both: the
+ *                 pendant keys 0 .. n - 1, then the split keys of a or b in ascending id; one
+ *                 serial fp64 sum from 0.0; the square is rounded on its own, then added (no fma).
+ *   Path2(a, b) = sum over i < j of (e_a(i, j) - e_b(i, j))^2, e(i, j) the number of edges between
+ *                 tips i and j; unsigned 64-bit integers, exact.
+ *   WPath2(a, b): the same with p(i, j) in fp64.  Root the tree at tip 0 and let l be the node of
+ *                 the path i .. j nearest tip 0 (tip 0 itself for i = 0); h(i -> l) is the sum of
+ *                 the edge lengths from tip i up to l, added serially from i's pendant edge (0.0
+ *                 for no edge); p(i, j) = h(i -> l) + h(j -> l).  The squares of p_a - p_b are
+ *                 rounded on their own and summed over the pairs in row-major order (i, then j)
+ *                 by DESIGN 4.17's segment rule: segments of 2048 consecutive pairs added serially
+ *                 from 0.0, the segment sums added serially in segment order.
+ *   split_len_sum[u] = the lengths of the edges that carry split u, added serially over the trees
+ *                 in ascending tree index; tip_len_sum[i] = tip i's pendant lengths likewise.
+ * Outputs, all nullable, a NULL one is not computed and changes no other: wrf_out, kf2_out,
+ * wpath2_out fp64 [n_rows][T] and path2_out uint64 [n_rows][T], trees 0 .. n_rows - 1 against
+ * all; n_unique_out [1] = U; split_len_sum_out with room for T (n - 3), the first U written;
+ * tip_len_sum_out [n].  n = 3 is valid: no split keys, three pendant keys, e = 2 for every pair.
+ * PU_E_ARG, before any device is touched: everything pu_treeset_compare refuses in its inputs; a
+ * null lengths; a length that is negative, NaN or infinite (the message names tree and edge);
+ * n_rows outside [0, T].
+ * Memory, beside pu_treeset_compare's T (n - 3) (8 nw + 44) bytes, nothing chunked: the keyed
+ * lengths and sorted ids T (28 n - 60) bytes; for path2_out or wpath2_out T (2n - 2) 16 bytes of
+ * rooted-tree arrays and T ceil4(n (n - 1) / 2) 2 bytes of integer paths (ceil4: rounded up to a
+ * multiple of 4); for wpath2_out T n (n - 1) / 2 8 bytes more; the output matrices.  PU_E_NOMEM
+ * where they do not fit. */
+int pu_treedist(int device, int n, int n_trees, int form, const int32_t *trees,
+                const int32_t *roots, const double *lengths, int n_rows, double *wrf_out,
+                double *kf2_out, uint64_t *path2_out, double *wpath2_out, int64_t *n_unique_out,
+                double *split_len_sum_out, double *tip_len_sum_out);
+/* Event timing (scripts/time_treedist.py): with pu_treedist_profile(device, 1) every call above
+ * records events between its stages; pu_treedist_kernel_ms returns the last call's times in ms:
+ * pu_treeset_compare's stages (splits and ids), the weighted stage (keyed lengths, per-tree sort,
+ * the merge kernel, the length sums), the paths per tree (rooting and the pair walk), the
+ * integer path reduction and the fp64 path reduction. */
+int pu_treedist_profile(int device, int on);
+int pu_treedist_kernel_ms(int device, double *ids_ms, double *weighted_ms, double *paths_ms,
+                          double *path2_ms, double *wpath2_ms);
+
 /* ---- Site concordance factors (normative; tests/concordance_reference.py
  * restates it) ----
  * The reference has no concordance factors; the rule is this project's own.  The alignment

@@ -185,6 +185,10 @@ SIGNATURES = {
                                     _P]),
     "pu_treeset_profile": (_c_int, [_c_int, _c_int]),
     "pu_treeset_kernel_ms": (_c_int, [_c_int, _P, _P, _P]),
+    "pu_treedist": (_c_int, [_c_int, _c_int, _c_int, _c_int, _P, _P, _P, _c_int, _P, _P, _P, _P, _P,
+                             _P, _P]),
+    "pu_treedist_profile": (_c_int, [_c_int, _c_int]),
+    "pu_treedist_kernel_ms": (_c_int, [_c_int, _P, _P, _P, _P, _P]),
     "pu_scf_counts": (_c_int, [_c_int, _c_int, _c_i64, _c_int, _c_int, _P, _P, _P, _P, _c_int,
                                _c_u64, _P, _P, _P]),
     "pu_scf_profile": (_c_int, [_c_int, _c_int]),

@@ -15,7 +15,8 @@
 // words are: nothing here hashes.
 //
 // The host checks the trees and brings every form to one device form (`cj`, below); the rest
-// runs on the device.
+// runs on the device.  The argument rules, the form conversion and the device stages are also
+// offered to pu_treedist.hip (pu_treeset_stages.h), which reads the id arrays they leave.
 //
 //   device form       cj [T][n-2][2]: op m of a tree makes cluster n + m from two children, a tip
 //                     (< n) or an earlier cluster n + m' (m' < m) -- pu_nj's join form, to which
@@ -81,6 +82,7 @@
 #include "pu_ctx.h"
 #include "pu_service.h"
 #include "pu_treeform.h"
+#include "pu_treeset_stages.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "pu_treeset.hip: gfx950 only, as the other kernel files of this library"
@@ -367,16 +369,12 @@ int mark(TreesetState &S, int i, hipStream_t st) {
     return PU_OK;
 }
 
-struct DevOut {
-    int32_t *edge_ids, *count, *rf;
-    int64_t *n_unique;
-    uint64_t *uniq_bits;
-};
-
-// everything on the device, queued on st
+// everything on the device, queued on st; ids (nullable): pu_treeset_stages.h
 int run_compare(int device, hipStream_t st, int n, int64_t T, const int32_t *d_cj,
-                const int32_t *d_y, const int32_t *d_emap, int n_rows, const DevOut &o) {
+                const int32_t *d_y, const int32_t *d_emap, int n_rows, const TreesetOut &o,
+                TreesetIds *ids) {
     TreesetState &S = g_ts[device];
+    if (ids) *ids = TreesetIds();
     StateScope scope(S, st);
     int rc;
     if ((rc = scope.rc)) return rc;
@@ -471,6 +469,11 @@ int run_compare(int device, hipStream_t st, int n, int64_t T, const int32_t *d_c
                        S.split_id.p, n, T, o.edge_ids);
     HIPCHK(nullptr, hipGetLastError());
     if ((rc = mark(S, 2, st))) return rc;
+    if (ids) {
+        ids->split_id = S.split_id.p;
+        ids->perm = perm;
+        ids->first = S.first.p;
+    }
 
     // RF
     if (o.rf && n_rows > 0) {
@@ -503,16 +506,17 @@ int run_compare(int device, hipStream_t st, int n, int64_t T, const int32_t *d_c
 
 }  // namespace
 
-extern "C" {
+// the names of this file's constants (kTile) mean other things in namespace pu: the stages stay
+// outside it, behind this door
+int pu::treeset_run(int device, hipStream_t st, int n, int64_t T, const int32_t *d_cj,
+                    const int32_t *d_y, const int32_t *d_emap, int n_rows, const TreesetOut &o,
+                    TreesetIds *ids) {
+    return run_compare(device, st, n, T, d_cj, d_y, d_emap, n_rows, o, ids);
+}
 
-int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *trees,
-                       const int32_t *roots, int n_rows, int32_t *edge_ids_out,
-                       int64_t *n_unique_out, uint64_t *uniq_bits_out, int32_t *uniq_count_out,
-                       int32_t *rf_out) {
-    const char *fn = "pu_treeset_compare";
-    int rc;
-    if (!trees || !edge_ids_out || !n_unique_out)
-        return set_err(nullptr, PU_E_ARG, "%s: null buffer", fn);
+int pu::treeset_check_args(const char *fn, int n, int n_trees, int form, const int32_t *trees,
+                           const int32_t *roots, int n_rows) {
+    if (!trees) return set_err(nullptr, PU_E_ARG, "%s: null buffer", fn);
     if (form != PU_TREES_OPS && form != PU_TREES_JOINS && form != PU_TREES_EDGES)
         return set_err(nullptr, PU_E_ARG, "%s: form = %d (PU_TREES_OPS, _JOINS, _EDGES)", fn, form);
     if (form != PU_TREES_EDGES && !roots)
@@ -525,14 +529,21 @@ int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *
                        n - 3);
     if (n_rows < 0 || n_rows > n_trees)
         return set_err(nullptr, PU_E_ARG, "%s: n_rows = %d is outside [0, %d]", fn, n_rows, n_trees);
-    // every form to the device form (header comment); a set too large for the host's memory is
-    // refused like one too large for the device's
+    return PU_OK;
+}
+
+// every form to the device form (header comment); a set too large for the host's memory is
+// refused like one too large for the device's
+int pu::treeset_device_form(const char *fn, int n, int n_trees, int form, const int32_t *trees,
+                            const int32_t *roots, TreesetForm &f) {
+    int rc;
     const int64_t T = n_trees;
     const int n_ops = n - 2, E = 2 * n - 3;
-    std::vector<int32_t> cj, y, emap;
+    std::vector<int32_t> &cj = f.cj, &y = f.y, &emap = f.emap;
     try {
         cj.resize((size_t)T * n_ops * 2);
         y.resize((size_t)T);
+        emap.clear();
         if (form == PU_TREES_EDGES) emap.resize((size_t)T * E);
         std::vector<int32_t> ops((size_t)n_ops * 3), slot((size_t)E), where((size_t)2 * n - 2);
         std::vector<char> state;
@@ -571,6 +582,25 @@ int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *
         return set_err(nullptr, PU_E_NOMEM, "%s: the host cannot hold %lld trees of %d tips", fn,
                        (long long)T, n);
     }
+    return PU_OK;
+}
+
+extern "C" {
+
+int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *trees,
+                       const int32_t *roots, int n_rows, int32_t *edge_ids_out,
+                       int64_t *n_unique_out, uint64_t *uniq_bits_out, int32_t *uniq_count_out,
+                       int32_t *rf_out) {
+    const char *fn = "pu_treeset_compare";
+    int rc;
+    if (!trees || !edge_ids_out || !n_unique_out)
+        return set_err(nullptr, PU_E_ARG, "%s: null buffer", fn);
+    if ((rc = treeset_check_args(fn, n, n_trees, form, trees, roots, n_rows))) return rc;
+    const int64_t T = n_trees;
+    const int E = 2 * n - 3;
+    TreesetForm f;
+    if ((rc = treeset_device_form(fn, n, n_trees, form, trees, roots, f))) return rc;
+    const std::vector<int32_t> &cj = f.cj, &y = f.y, &emap = f.emap;
     if ((rc = check_device(device))) return rc;
     DeviceGuard g(device);
     HostCall h(device);
@@ -578,13 +608,13 @@ int pu_treeset_compare(int device, int n, int n_trees, int form, const int32_t *
     const int32_t *d_cj = h.to_device(cj.data(), cj.size());
     const int32_t *d_y = h.to_device(y.data(), y.size());
     const int32_t *d_emap = emap.empty() ? nullptr : h.to_device(emap.data(), emap.size());
-    DevOut o;
+    TreesetOut o;
     o.edge_ids = h.alloc<int32_t>((size_t)T * E);
     o.n_unique = h.alloc<int64_t>(1);
     o.uniq_bits = uniq_bits_out ? h.alloc<uint64_t>(N * nw) : nullptr;
     o.count = uniq_count_out ? h.alloc<int32_t>(N) : nullptr;
     o.rf = rf_out && n_rows ? h.alloc<int32_t>((size_t)n_rows * T) : nullptr;
-    if (!h.rc) h.rc = run_compare(device, h.st, n, T, d_cj, d_y, d_emap, n_rows, o);
+    if (!h.rc) h.rc = treeset_run(device, h.st, n, T, d_cj, d_y, d_emap, n_rows, o, nullptr);
     h.to_host(edge_ids_out, o.edge_ids, (size_t)T * E);
     h.to_host(n_unique_out, o.n_unique, 1);
     if (o.rf) h.to_host(rf_out, o.rf, (size_t)n_rows * T);

@@ -90,7 +90,10 @@ consensus), every internal node labelled with its split's share in percent, no b
 ``--compare-trees FILE`` compares the run's final tree (tree 0) with the Newick trees of FILE, one
 per line (trees 1, 2, ...): after the ``lnL = `` line (and the ``--test-trees`` table) come one line
 ``rf i: d_0 d_1 ...`` per tree, its Robinson-Foulds distances to all of them, and ``topologies = k
-distinct of m``;
+distinct of m``; with ``--tree-metric {wrf,kf,path,wpath}`` one line ``<metric> i: d_0 d_1 ...``
+per tree follows the ``rf`` lines: the weighted Robinson-Foulds, branch-score, path-difference or
+weighted path-difference distances (``treeset.distances``; tree 0 with the run's final lengths,
+every tree of FILE needs a length on every edge), printed with ``repr``;
 ``-s aln.fasta -m MODEL --lmap [Q]`` needs no ``-t`` either: likelihood mapping
 (``phylo_utils_amd.lmap``) of Q quartets (default min(C(n,4), 25 n), the seed of
 ``--seed``; with ``--lmap-clusters FILE``, four lines of taxon names, one taxon of each line per
@@ -303,6 +306,11 @@ def parse_cli(argv=None):
                     dest="consensus_threshold",
                     help="with --consensus: keep the splits in more than the share P of the "
                          "replicates (0.5 to 1; 1: in all of them; default 0.5)")
+    ap.add_argument("--tree-metric", type=str, default=None, dest="tree_metric",
+                    choices=["wrf", "kf", "path", "wpath"],
+                    help="with --compare-trees: after the rf lines, one '<metric> i: ...' line per "
+                         "tree with its weighted RF, branch-score, path or weighted path "
+                         "distances to all of them (every tree needs branch lengths)")
     ap.add_argument("--compare-trees", type=str, default=None, metavar="FILE",
                     dest="compare_trees",
                     help="after the lnL line: Robinson-Foulds distances between the final tree "
@@ -435,6 +443,9 @@ def validate_args(args):
             raise ValueError("--consensus needs --bootstrap")
         if not 0.5 <= getattr(args, "consensus_threshold", 0.5) <= 1.0:
             raise ValueError("--consensus-threshold needs a share within [0.5, 1]")
+    if getattr(args, "tree_metric", None) is not None \
+            and getattr(args, "compare_trees", None) is None:
+        raise ValueError("--tree-metric needs --compare-trees")
     if getattr(args, "compare_trees", None) is not None:
         if getattr(args, "distances", False) or getattr(args, "simulate", None) is not None:
             raise ValueError("--compare-trees excludes --simulate and --distances")
@@ -696,6 +707,13 @@ def run_compare_trees(args, tm):
     res = treeset.compare(trees, names=names, device=args.device)
     lines = ["rf {}: {}".format(i, " ".join(str(int(d)) for d in row))
              for i, row in enumerate(res.rf)]
+    metric = getattr(args, "tree_metric", None)
+    if metric is not None:
+        from .tree import with_lengths
+        current = with_lengths(tm.tree, tm.traversal.brlens)
+        d = treeset.distances([current] + trees[1:], metric, names=names, device=args.device)
+        lines += ["{} {}: {}".format(metric, i, " ".join(repr(float(x)) for x in row))
+                  for i, row in enumerate(d)]
     k = len(set(int(c) for c in treeset.topology_classes(res)))
     return lines + ["topologies = {} distinct of {}".format(k, len(trees))]
 

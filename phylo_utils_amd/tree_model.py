@@ -841,6 +841,22 @@ class TreeModel(object):
         names = sorted(self.names, key=self.names.get)
         return int(treeset.rf_distances([self.tree, other], names, device=self.device)[0, 1])
 
+    def tree_distance(self, other, metric="kf"):
+        """The distance between the model's current tree with its current branch lengths and
+        `other` (a ``Tree`` or Newick over the same names, with a length on every edge), a float:
+        `metric` ``"wrf"``, ``"kf"``, ``"path"`` or ``"wpath"`` of ``treeset.distances`` (DESIGN
+        4.31)."""
+        from . import treeset
+        from .tree import with_lengths
+        if getattr(self, "tree", None) is None:
+            raise ValueError("No tree has been set")
+        if not isinstance(metric, str):
+            raise ValueError("metric is one name, not %r" % (metric,))
+        names = sorted(self.names, key=self.names.get)
+        current = with_lengths(self.tree, self.traversal.brlens)
+        return float(treeset.distances([current, other], metric, names, rows=1,
+                                       device=self.device)[0, 1])
+
     def map_support(self, trees):
         """Label the model's current tree with the support of the tree set `trees` -- any form
         ``treeset.compare`` takes, arrays over the alignment's rows: the replicates of

@@ -17,8 +17,14 @@ as ``parsimony.stepwise_addition`` returns it (or a list of edge lists).  Each f
 edge order: op order (edge ``2i`` = (left_i, parent_i), ``2i+1`` = (right_i, parent_i), then the
 root edge) for the first three, the list's own for an edge batch.
 
+Trees with branch lengths: ``distances`` gives the weighted Robinson-Foulds,
+branch-score (Kuhner-Felsenstein), path-difference and weighted path-difference distances,
+``split_lengths`` the mean length of every split and of every tip's edge, which ``consensus``
+writes onto its tree.  ``Tree`` and Newick bring their own lengths; the array forms take
+``lengths [T][2n-3]`` in the form's edge order.
+
 There is no host fallback for the device work: splits, ids, counts and distances come from the
-HIP kernels of ``pu_treeset.hip``.
+HIP kernels of ``pu_treeset.hip`` and ``pu_treedist.hip``.
 """
 from __future__ import annotations
 
@@ -29,9 +35,10 @@ import numpy as np
 from . import _native as N
 from .bootstrap import _join_arrays, support_label
 from .parsimony import _prepared_schedule
-from .tree import Node, Traversal, Tree, prepare_tree
+from .tree import Node, Traversal, Tree, parse_newick, prepare_tree
 
 FORMS = {"ops": 0, "joins": 1, "edges": 2}
+METRICS = ("wrf", "kf", "path", "wpath")
 
 
 class TreeSetResult(object):
@@ -84,6 +91,17 @@ def _joins_as_ops(joins):
     return ops
 
 
+def _batch_prepared(prepared, names):
+    """_batch of trees that ``prepare_tree`` has prepared already."""
+    if names is None:
+        names = sorted(x.label for x in prepared[0].leaf_nodes())
+    sched = [_prepared_schedule(t, names) for t in prepared]
+    ops = np.ascontiguousarray(np.stack([s[0] for s in sched]), dtype=np.int32)
+    ops = ops.reshape(len(sched), -1, 3)
+    roots = np.ascontiguousarray(np.stack([s[1] for s in sched]), dtype=np.int32)
+    return "ops", ops, roots, names, [s[2] for s in sched]
+
+
 def _batch(trees, names, form):
     """(form, arrays int32 [T][..], roots [T][2] or None, names, pairs) of a tree set."""
     if form is not None and form not in FORMS:
@@ -91,14 +109,7 @@ def _batch(trees, names, form):
     if isinstance(trees, (str, Tree)):
         trees = [trees]
     if isinstance(trees, list) and trees and all(isinstance(t, (str, Tree)) for t in trees):
-        prepared = [prepare_tree(t) for t in trees]
-        if names is None:
-            names = sorted(x.label for x in prepared[0].leaf_nodes())
-        sched = [_prepared_schedule(t, names) for t in prepared]
-        ops = np.ascontiguousarray(np.stack([s[0] for s in sched]), dtype=np.int32)
-        ops = ops.reshape(len(sched), -1, 3)
-        roots = np.ascontiguousarray(np.stack([s[1] for s in sched]), dtype=np.int32)
-        return "ops", ops, roots, names, [s[2] for s in sched]
+        return _batch_prepared([prepare_tree(t) for t in trees], names)
     if isinstance(trees, (tuple, list)) and trees and not isinstance(trees[0], (str, Tree)):
         shapes = [np.shape(x) for x in trees]
         if len(shapes[0]) == 2 and shapes[0][1] == 2 and shapes[0][0] % 2 == 1 \
@@ -197,26 +208,39 @@ def split_tips(bits, n):
     return np.flatnonzero(np.unpackbits(b, bitorder="little")[:n])
 
 
-def consensus(result, threshold=0.5, min_length=None):
+def consensus(result, threshold=0.5, min_length=None, lengths=None):
     """The majority-rule consensus tree of `result`'s trees: the splits with ``count / T >
     threshold`` -- at threshold 1.0 those with ``count == T``, the strict consensus -- nested by
     ascending tip count into a ``tree.Tree`` that may hold polytomies.  Every internal node that
     carries a split is labelled ``bootstrap.support_label(count / T)``; edges carry no length
     (`min_length` is accepted for the tree builders' common signature and has nothing to act
-    on).  Thresholds outside [0.5, 1] are refused: below 0.5 the splits need not be compatible
-    (greedy consensus is not offered)."""
+    on) unless `lengths` = ``(split_mean [U], tip_mean [n])`` of ``split_lengths`` is given: then
+    the edge above every kept split and every tip's edge carries its mean length.  A kept split
+    that holds all tips but tip 0 and one other cannot occur (it would be trivial), so no two
+    kept nodes share an edge.  Thresholds outside [0.5, 1] are refused: below 0.5 the splits need
+    not be compatible (greedy consensus is not offered)."""
     threshold = float(threshold)
     if not 0.5 <= threshold <= 1.0:
         raise ValueError("threshold must be within [0.5, 1], not %r" % threshold)
     n, T = result.n, result.n_trees
+    if lengths is not None:
+        split_mean, tip_mean = (np.asarray(x, dtype=np.float64).reshape(-1) for x in lengths)
+        if len(split_mean) != result.n_unique or len(tip_mean) != n:
+            raise ValueError("lengths is (split_mean [%d], tip_mean [%d]), not [%d] and [%d]"
+                             % (result.n_unique, n, len(split_mean), len(tip_mean)))
     names = result.names if result.names is not None else [str(i) for i in range(n)]
     count = np.asarray(result.count, dtype=np.int64)
     keep = np.flatnonzero(count == T if threshold >= 1.0 else count > threshold * T)
     tips = [split_tips(result.bits[u], n) for u in keep]
     order = sorted(range(len(keep)), key=lambda i: (len(tips[i]), i))
     top = [Node(str(x)) for x in names]  # per tip: the highest node made so far that holds it
+    if lengths is not None:
+        for x, node in enumerate(top):
+            node.length = float(tip_mean[x])
     for i in order:
         node = Node(support_label(count[keep[i]] / float(T)))
+        if lengths is not None:
+            node.length = float(split_mean[keep[i]])
         seen = set()
         for x in tips[i]:
             c = top[x]
@@ -316,6 +340,133 @@ def support(ref, trees, names=None, device=0, form=None):
     return out, prepared
 
 
+def _tree_lengths(pairs_of, prepared):
+    """float64 [T][2n-3]: the lengths of prepared trees in op edge order (the root edge's as
+    ``Traversal`` gives it)."""
+    out = []
+    for pairs, p in zip(pairs_of, prepared):
+        bl = Traversal(p).brlens
+        out.append([float(bl[pair]) for pair in pairs])
+    return np.array(out, dtype=np.float64)
+
+
+def _refuse_missing_lengths(trees):
+    """A ``Tree`` or Newick with an edge that has no length is refused, the tree named."""
+    for t, tree in enumerate(trees):
+        parsed = parse_newick(tree) if isinstance(tree, str) else tree
+        seed = parsed.seed_node
+        for node in seed.postorder():
+            if node is not seed and node.length is None:
+                raise ValueError("tree %d: the edge above %s has no length" % (
+                    t, repr(node.label) if node.label is not None else "an internal node"))
+
+
+def _batch_with_lengths(trees, names, form, lengths):
+    """_batch and float64 lengths [T][2n-3] in the form's edge order, checked."""
+    if isinstance(trees, (str, Tree)):
+        trees = [trees]
+    own = isinstance(trees, list) and trees and all(isinstance(t, (str, Tree)) for t in trees)
+    if own:
+        if lengths is not None:
+            raise ValueError("Tree and Newick input brings its own lengths")
+        _refuse_missing_lengths(trees)
+        if form not in (None, "ops"):
+            raise ValueError("form=%r, but Tree and Newick input is the ops form" % form)
+        prepared = [prepare_tree(t) for t in trees]
+        form, a, roots, names, pairs = _batch_prepared(prepared, names)
+        lengths = _tree_lengths(pairs, prepared)
+    else:
+        form, a, roots, names, pairs = _batch(trees, names, form)
+        if lengths is None:
+            raise ValueError("the array forms need lengths [T][2n-3] in the form's edge order")
+        lengths = np.ascontiguousarray(lengths, dtype=np.float64)
+    T = len(a)
+    n = a.shape[1] + 2 if form != "edges" else (a.shape[1] + 3) // 2
+    if form == "edges" and a.shape[1] != 2 * n - 3:
+        raise ValueError("an edge list has 2n-3 rows, not %d" % a.shape[1])
+    if lengths.ndim == 1 and T == 1:
+        lengths = lengths[None]
+    if lengths.shape != (T, 2 * n - 3):
+        raise ValueError("lengths must be [%d][%d], not %r" % (T, 2 * n - 3, lengths.shape))
+    bad = np.argwhere(~(np.isfinite(lengths) & (lengths >= 0.0)))
+    if len(bad):
+        raise ValueError("tree %d edge %d: length %r is not a finite number >= 0"
+                         % (bad[0][0], bad[0][1], float(lengths[tuple(bad[0])])))
+    if names is not None and len(names) != n:
+        raise ValueError("%d names for trees of %d tips" % (len(names), n))
+    return form, a, roots, names, pairs, np.ascontiguousarray(lengths), n
+
+
+def _treedist(form, a, roots, lengths, n, k, want, sums, device):
+    """pu_treedist: dict of the matrices named in `want` ("wrf", "kf2", "path2", "wpath2") and,
+    with `sums`, "U", "split_sum" [U] and "tip_sum" [n]."""
+    T = len(a)
+    out = {}
+    for key in want:
+        out[key] = np.zeros((k, T), dtype=np.uint64 if key == "path2" else np.float64)
+    buf = {key: (out[key] if k > 0 and key in out else None)
+           for key in ("wrf", "kf2", "path2", "wpath2")}
+    U = np.zeros(1, dtype=np.int64) if sums else None
+    ssum = np.zeros(max(T * (n - 3), 1), dtype=np.float64) if sums else None
+    tsum = np.zeros(n, dtype=np.float64) if sums else None
+    N.check(N.lib().pu_treedist(int(device), n, T, FORMS[form], N.ptr(a), N.ptr(roots),
+                                N.ptr(lengths), k, N.ptr(buf["wrf"]), N.ptr(buf["kf2"]),
+                                N.ptr(buf["path2"]), N.ptr(buf["wpath2"]), N.ptr(U), N.ptr(ssum),
+                                N.ptr(tsum)), None, "pu_treedist")
+    if sums:
+        out["U"] = int(U[0])
+        out["split_sum"] = ssum[:out["U"]].copy()
+        out["tip_sum"] = tsum
+    return out
+
+
+_RAW = {"wrf": "wrf", "kf": "kf2", "path": "path2", "wpath": "wpath2"}
+
+
+def distances(trees, metric, names=None, lengths=None, rows=None, device=0, form=None,
+              squared=False):
+    """pu_treedist: distances between trees with branch lengths, float64 [rows][T].  `metric`:
+    ``"wrf"`` (weighted Robinson-Foulds, Robinson & Foulds 1979), ``"kf"`` (branch score, Kuhner
+    & Felsenstein 1994), ``"path"`` (topological path difference, Steel & Penny 1993),
+    ``"wpath"`` (the same on patristic distances), or a tuple of them: then a dict of arrays.
+    `rows` as in ``compare``.  ``Tree`` and Newick input brings its own lengths (one without a
+    length on some edge is refused); the array forms need `lengths` [T][2n-3] in the form's edge
+    order.  ``kf``, ``path`` and ``wpath`` are the host's square roots of the device's sums of
+    squares; `squared` True returns those sums themselves (``path``: uint64, exact)."""
+    one = isinstance(metric, str)
+    metrics = (metric,) if one else tuple(metric)
+    for m in metrics:
+        if m not in METRICS:
+            raise ValueError("metric must be one of %s, not %r" % (list(METRICS), m))
+    if not metrics:
+        raise ValueError("no metric")
+    form, a, roots, names, _, lengths, n = _batch_with_lengths(trees, names, form, lengths)
+    T = len(a)
+    k = T if rows is None else int(rows)
+    if not 0 <= k <= T:
+        raise ValueError("rows = %d is outside [0, %d]" % (k, T))
+    raw = _treedist(form, a, roots, lengths, n, k, [_RAW[m] for m in metrics], False, device)
+    out = {}
+    for m in metrics:
+        x = raw[_RAW[m]]
+        out[m] = x if m == "wrf" or squared else np.sqrt(x.astype(np.float64))
+    return out[metric] if one else out
+
+
+def split_lengths(trees, names=None, lengths=None, device=0, form=None):
+    """(result, split_mean [U], tip_mean [n]): ``compare``'s ``TreeSetResult`` of the tree set
+    (no distances) and the mean length of every split of ``result.bits`` over the trees that hold
+    it (the device's sum in ascending tree order / ``count``) and of every tip's edge (sum / T)."""
+    form, a, roots, names, pairs, lengths, n = _batch_with_lengths(trees, names, form, lengths)
+    arg = a if form == "edges" else (a, roots)
+    result = compare(arg, names, 0, device, form)
+    result.pairs = pairs
+    raw = _treedist(form, a, roots, lengths, n, 0, [], True, device)
+    if raw["U"] != result.n_unique:
+        raise RuntimeError("pu_treedist and pu_treeset_compare disagree on the split table")
+    return result, raw["split_sum"] / result.count, raw["tip_sum"] / float(result.n_trees)
+
+
 def profile(on, device=0):
     """Switch the event timing of ``compare`` on `device` on or off."""
     N.check(N.lib().pu_treeset_profile(int(device), int(bool(on))), None, "pu_treeset_profile")
@@ -328,3 +479,17 @@ def kernel_ms(device=0):
     N.check(N.lib().pu_treeset_kernel_ms(int(device), ctypes.byref(s), ctypes.byref(i),
                                          ctypes.byref(r)), None, "pu_treeset_kernel_ms")
     return s.value, i.value, r.value
+
+
+def distance_profile(on, device=0):
+    """Switch the event timing of ``distances`` and ``split_lengths`` on `device` on or off."""
+    N.check(N.lib().pu_treedist_profile(int(device), int(bool(on))), None, "pu_treedist_profile")
+
+
+def distance_kernel_ms(device=0):
+    """(ids, weighted, paths, path2, wpath2): the stage times of the last pu_treedist call on
+    `device` while profiling, in ms."""
+    v = [ctypes.c_double() for _ in range(5)]
+    N.check(N.lib().pu_treedist_kernel_ms(int(device), *[ctypes.byref(x) for x in v]), None,
+            "pu_treedist_kernel_ms")
+    return tuple(x.value for x in v)
